@@ -1,7 +1,15 @@
 """Slide-encoder throughput benchmark (BASELINE.json metric) on 1..8 MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--tiles T]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--tiles T] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run does what the headline figure needs and no more: set up, W warm-up steps, K timed steps, one
+JSON line (metric / value / unit / ms_per_step / ...).  `--dump-outputs DIR` also writes what the last timed
+step returned to its caller as DIR/<name>.npy (float32): the model is seeded, so two builds run with the
+same arguments see identical inputs and can be compared output for output.  `--full` adds everything else
+to the line, each part a run of its own after the timed steps: the per-kernel timing pass (attention / merge
+rooflines, kernel_ms_per_step, the per-rank sequence-parallel report), the 256k-slide line on one GPU and the
+CPU baselines.
 
 Without a launcher (`WORLD_SIZE` unset), `--gpus N > 1` starts the N ranks itself: it runs
 torch.distributed.run as a child process before anything touches the GPU.  Under a launcher,
@@ -19,9 +27,9 @@ Multi-GPU (one process per GPU), --mode:
   mixed    C5: a batch of 32 slides of 2k-100k tiles (log-uniform, seed 3), LPT-assigned to the
            ranks (batch.py, data parallel, one all-reduce of the outputs at the end), each rank's
            slides varlen-packed into one forward; value = batch tiles / time ("strong").
-Rank 0 prints ONE JSON line including the attention kernel's roofline (HIP events around
-every gp_dilated_attn_fwd launch in the timed region) and a CPU baseline (the fp32 oracle on
-a bounded sample of the same workload, timed on this host).
+Rank 0 prints ONE JSON line; with --full it includes the attention kernel's roofline (HIP events
+around every gp_dilated_attn_fwd launch of an eager pass after the timed region) and a CPU baseline
+(the fp32 oracle on a bounded sample of the same workload, timed on this host).
 """
 import argparse
 import json
@@ -199,6 +207,24 @@ def spawn_ranks(ngpus):
     return subprocess.call(cmd)
 
 
+def named_outputs(out, mixed):
+    """(name, tensor) of everything a step returned: the forward's list of [B, E] embeddings, or (mixed) that
+    list for every slide of the batch."""
+    if mixed:
+        return [("slide%02d_embed%02d" % (i, k), o) for i, outs in enumerate(out) for k, o in enumerate(outs)]
+    return [("embed%02d" % k, o) for k, o in enumerate(out)]
+
+
+def dump_outputs(path, named, prefix=""):
+    """Write each output as path/<prefix><name>.npy in float32.  The embeddings are [B, E] per layer (and per
+    slide): a few MB at the most for any --tiles, so they are written whole."""
+    arrs = [(name, o.detach().float().cpu().numpy()) for name, o in named]
+    assert sum(a.nbytes for _, a in arrs) <= 64 << 20
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrs:
+        np.save(os.path.join(path, prefix + name + ".npy"), a)
+
+
 def pmc_traffic(n_tiles, kernel):
     """HBM bytes per launch of `kernel` from the committed rocprofv3 PMC summary (tools/pmc_bench.sh ->
     profiles/pmc_traffic.json), or None when it was collected on a different workload."""
@@ -216,6 +242,97 @@ def pmc_traffic(n_tiles, kernel):
     return round(max(k["hbm_bytes_per_launch"] for k in ks))
 
 
+def kernel_report(args, model, rank, world, sp, mixed, sizes, monitor, L, segs, ratios):
+    """--full: the result keys that come from the per-kernel timing pass (runtime.TIMER's HIP events): the
+    attention and merge kernels against their rooflines, kernel_ms_per_step and, under sequence parallelism,
+    the sparsify roofline and every rank's report."""
+    from gigapath import runtime
+    kt = runtime.TIMER.totals_ms()
+    att_flops_launch = runtime.attention_valid_flops(L, segs, ratios, 16, 48)
+    if mixed:
+        # varlen packing: one attention launch per layer covers every slide of this rank
+        from gigapath import batch as _b
+        mine = _b.lpt_assign([_b.slide_cost(n, segs, ratios) for n in sizes], world)[rank]
+        att_flops_launch = sum(runtime.attention_valid_flops(sizes[i] + 1, segs, ratios, 16, 48) for i in mine)
+    n_att, ms_att = kt.get("attn", (0, 0.0))
+    if sp:          # (the SP engine labels its launches by exchange phase: attn_local / attn_A / attn_B)
+        ms_att = sum(v[1] for k, v in kt.items() if k.startswith("attn"))
+        # this rank's attention launches cover its query window: price them with its share of the
+        # valid FLOPs (two launches per layer: local branches, then exchanged ones)
+        plan = model._sp.plan
+        a_w, b_w = plan.bounds[rank]
+        att_flops_launch = runtime.attention_valid_flops_window(L, segs, ratios, 16, 48, a_w, b_w)
+        n_att = args.timing_steps * len(model.encoder.layers)   # per layer: both launches together
+    avg_att_s = ms_att / max(n_att, 1) / 1e3
+    achieved = att_flops_launch / avg_att_s / 1e12 if avg_att_s > 0 else 0.0
+    plain = not (sp or mixed)          # the PMC summary was collected on the plain C3 run
+    traffic = pmc_traffic(args.tiles, "dilated_attn32_kernel<48, true, 0,") if plain else None
+    # HBM-bound merge kernel: algorithmic bytes per launch (DESIGN.md §3) over its live launch time
+    n_mg, ms_mg = kt.get("merge", (0, 0.0))
+    if sp:
+        merge_tok = b_w - a_w
+    elif mixed:
+        merge_tok = sum(sizes[i] + 1 for i in mine)
+    else:
+        merge_tok = L
+    merge_bytes = runtime.merge_bytes(L, segs, ratios, 16, 48) * merge_tok / L
+    merge_gbs = merge_bytes / (ms_mg / max(n_mg, 1) / 1e3) / 1e9 if ms_mg > 0 else 0.0
+    rep = {
+        "roofline": {"bound": "mfma", "kernel": "gp_dilated_attn_fwd", "achieved": round(achieved, 2),
+                     "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
+                     "traffic": traffic, "flops_per_launch": att_flops_launch, "avg_launch_ms": round(avg_att_s * 1e3, 4),
+                     "launches": n_att},
+        "attn_mfma_util_pct": round(100 * achieved / PEAK_BF16_TFLOPS, 2),
+        "merge_roofline": {"bound": "hbm", "kernel": "gp_branch_merge_ln", "achieved": round(merge_gbs, 1),
+                           "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(merge_gbs / PEAK_HBM_GBS, 4),
+                           "traffic": pmc_traffic(args.tiles, "branch_merge_v3_kernel<5") if plain else None,
+                           "bytes_per_launch": merge_bytes},
+        "kernel_ms_per_step": {k: round(v[1] / args.timing_steps, 3) for k, v in sorted(kt.items())},
+    }
+    if sp:
+        import torch.distributed as dist
+        # the SP gather (gp_dilated_sparsify_dests): per branch that crosses a cut, read the K and V
+        # head-group columns of this rank's tokens (2*C_b bf16 each) and write one row per destination
+        # chunk (transfer-free branches are read in place by the attention: no sparsify bytes)
+        sp_bytes = sum((b_w - a_w) * 2 * plan.C[b] * 2 + sum(plan.send_splits(rank, b)) * 2 * plan.C[b] * 2
+                       for b in range(len(plan.C)) if not plan.no_xfer[b])
+        n_sp, ms_sp = kt.get("sparsify", (0, 0.0))
+        sp_gbs = sp_bytes / (ms_sp / max(n_sp, 1) / 1e3) / 1e9 if ms_sp > 0 else 0.0
+        rep["sparsify_roofline"] = {"bound": "hbm", "kernel": "gp_dilated_sparsify_dests",
+                                    "achieved": round(sp_gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                                    "frac": round(sp_gbs / PEAK_HBM_GBS, 4), "traffic": None,
+                                    "bytes_per_launch": sp_bytes}
+        # every rank's view (shard, xGMI bytes, exposed exchange wait, kernel rooflines), gathered
+        mine_rep = sp_rank_report(model, kt, rank, args.timing_steps, L, segs, ratios, monitor)
+        reps = [None] * world
+        dist.all_gather_object(reps, mine_rep)
+        rep["sp_ranks"] = reps
+        rep["sp_exchange_exposed_ms_per_layer_max"] = max(
+            r["exchange_exposed"]["ms_per_layer"] for r in reps)
+    return rep
+
+
+def c4_same_gpu(model, dev):
+    """--full, N = 1: the C4 256k slide on this one GPU, same process: the N > 1 lines shard THIS workload, so
+    their speedup over this line (not over the 70k `value`) is the sequence-parallel scaling."""
+    x4, c4 = make_slide(256000, seed=1)
+    x4t, c4t = torch.from_numpy(x4).to(dev), torch.from_numpy(c4).to(dev)
+    del x4, c4
+    print("bench: C4 256k reference line on this GPU ...", file=sys.stderr, flush=True)
+    with torch.no_grad():
+        for _ in range(2):
+            model(x4t, c4t, all_layer_embed=True)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for _ in range(3):
+            model(x4t, c4t, all_layer_embed=True)
+        torch.cuda.synchronize(dev)
+        e4 = time.perf_counter() - t0
+    return {"workload": "C4 slide (256,000 tiles) forward on this one GPU, all_layer_embed=True, HIP-graph replay",
+            "tiles_per_s": round(256000 * 3 / e4, 2), "ms_per_step": round(e4 / 3 * 1e3, 3), "steps": 3,
+            "note": "the N > 1 lines shard this workload: their speedup over this line is the C4 scaling"}
+
+
 def main():
     if os.environ.get("GP_BENCH_TRACE_AFTER"):           # debugging aid: dump every thread's stack
         import faulthandler
@@ -226,17 +343,24 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--tiles", type=int, default=None,
                     help="slide size (default 70000; 256000 for --mode sp at N > 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the per-kernel timing pass (rooflines), the 256k-slide line and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--mode", choices=["sp", "replica", "mixed"], default="sp")
-    ap.add_argument("--timing-steps", type=int, default=2, help="eager steps with per-kernel HIP events")
+    ap.add_argument("--timing-steps", type=int, default=2,
+                    help="--full: eager steps with per-kernel HIP events")
     ap.add_argument("--mixed-slides", type=int, default=32, help="--mode mixed: slides in the batch")
     ap.add_argument("--no-graphs", action="store_true", help="eager launches instead of HIP graph replay")
-    ap.add_argument("--no-cpu-full", action="store_true", help="skip the full C1/C2 CPU forwards")
+    ap.add_argument("--no-cpu-full", action="store_true", help="--full: skip the full C1/C2 CPU forwards")
     ap.add_argument("--no-c4-ref", action="store_true",
-                    help="N = 1: skip the 256k-slide line (the workload the N > 1 runs shard)")
+                    help="--full, N = 1: skip the 256k-slide line (the workload the N > 1 runs shard)")
     ap.add_argument("--dry-run", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -268,6 +392,7 @@ def main():
 
     import contextlib
     from gigapath import runtime, slide_encoder
+    torch.manual_seed(0)    # the random-init weights are inputs too: the same in every run and on every rank
     with contextlib.redirect_stdout(sys.stderr):       # keep stdout to the one JSON line
         model = slide_encoder.create_model("", ARCH, 1536).to(dev).eval()
     model.validate_positions = True
@@ -287,7 +412,7 @@ def main():
         args.tiles = sum(sizes)
 
         def step():
-            return batch.encode_slides(model, slides, all_layer_embed=True)[0]
+            return batch.encode_slides(model, slides, all_layer_embed=True)
     else:
         x, coords = make_slide(args.tiles, seed=1 if sp else 1 + rank)
         xt = torch.from_numpy(x).to(dev)
@@ -319,67 +444,45 @@ def main():
         if world > 1:
             dist.barrier()
         t1 = time.perf_counter()
-        # per-kernel timing pass (HIP events around every hot launch, on the launch stream): an
-        # eager run of the same workload after the timed region, so the events do not add host
-        # work to the timed steps; a kernel's duration does not depend on how it was launched
-        runtime.TIMER.reset()
-        runtime.TIMER.enabled = True
-        if monitor is not None:              # drop the warm-up's records (it included graph capture)
-            monitor._pending.clear()
-            monitor.records.clear()
-            model._sp.set_monitor(monitor)
-        for _ in range(args.timing_steps):
-            step()
-        torch.cuda.synchronize(dev)
-        runtime.TIMER.enabled = False
-        if monitor is not None:
-            model._sp.set_monitor(None)
+        named = named_outputs(out, mixed)
+        assert all(torch.isfinite(o).all() for _, o in named)
+        if args.dump_outputs:
+            # SP and the mixed batch return the same outputs on every rank; replicas encode a slide each
+            own = world > 1 and not (sp or mixed)
+            if own or rank == 0:
+                dump_outputs(args.dump_outputs, named, ("rank%d_" % rank) if own else "")
+        if args.full:
+            # per-kernel timing pass (HIP events around every hot launch, on the launch stream): an
+            # eager run of the same workload after the timed region, so the events do not add host
+            # work to the timed steps; a kernel's duration does not depend on how it was launched
+            runtime.TIMER.reset()
+            runtime.TIMER.enabled = True
+            if monitor is not None:              # drop the warm-up's records (it included graph capture)
+                monitor._pending.clear()
+                monitor.records.clear()
+                model._sp.set_monitor(monitor)
+            for _ in range(args.timing_steps):
+                step()
+            torch.cuda.synchronize(dev)
+            runtime.TIMER.enabled = False
+            if monitor is not None:
+                model._sp.set_monitor(None)
     elapsed = t1 - t0
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-    assert all(torch.isfinite(o).all() for o in out)
 
-    kt = runtime.TIMER.totals_ms()
     segs = model.encoder.layers[0].self_attn.args.segment_length
     ratios = model.encoder.layers[0].self_attn.args.dilated_ratio
     L = args.tiles + 1
-    att_flops_launch = runtime.attention_valid_flops(L, segs, ratios, 16, 48)
-    if mixed:
-        # varlen packing: one attention launch per layer covers every slide of this rank
-        from gigapath import batch as _b
-        mine = _b.lpt_assign([_b.slide_cost(n, segs, ratios) for n in sizes], world)[rank]
-        att_flops_launch = sum(runtime.attention_valid_flops(sizes[i] + 1, segs, ratios, 16, 48) for i in mine)
-    n_att, ms_att = kt.get("attn", (0, 0.0))
-    if sp:          # (the SP engine labels its launches by exchange phase: attn_local / attn_A / attn_B)
-        ms_att = sum(v[1] for k, v in kt.items() if k.startswith("attn"))
-        # this rank's attention launches cover its query window: price them with its share of the
-        # valid FLOPs (two launches per layer: local branches, then exchanged ones)
-        plan = model._sp.plan
-        a_w, b_w = plan.bounds[rank]
-        att_flops_launch = runtime.attention_valid_flops_window(L, segs, ratios, 16, 48, a_w, b_w)
-        n_att = args.timing_steps * len(model.encoder.layers)   # per layer: both launches together
-    avg_att_s = ms_att / max(n_att, 1) / 1e3
-    achieved = att_flops_launch / avg_att_s / 1e12 if avg_att_s > 0 else 0.0
     if mixed:   # whole batch (all ranks)
         total_tf = sum(runtime.gemm_flops(1, n, 768, 3072, 1536, 12)
                        + 12 * runtime.attention_valid_flops(n + 1, segs, ratios, 16, 48) for n in sizes) / 1e12
     else:       # one slide (SP: shared by the ranks; replicas: one per rank)
         total_tf = (runtime.gemm_flops(1, args.tiles, 768, 3072, 1536, 12)
                     + 12 * runtime.attention_valid_flops(L, segs, ratios, 16, 48)) / 1e12
-    plain = not (sp or mixed)          # the PMC summary was collected on the plain C3 run
-    traffic = pmc_traffic(args.tiles, "dilated_attn32_kernel<48, true, 0,") if plain else None
-    # HBM-bound merge kernel: algorithmic bytes per launch over its live launch time
-    n_mg, ms_mg = kt.get("merge", (0, 0.0))
-    if sp:
-        merge_tok = b_w - a_w
-    elif mixed:
-        merge_tok = sum(sizes[i] + 1 for i in mine)
-    else:
-        merge_tok = L
-    merge_bytes = runtime.merge_bytes(L, segs, ratios, 16, 48) * merge_tok / L
-    merge_gbs = merge_bytes / (ms_mg / max(n_mg, 1) / 1e3) / 1e9 if ms_mg > 0 else 0.0
+    plain = not (sp or mixed)
     value = (1 if (sp or mixed) else world) * args.tiles * args.steps / elapsed
     ms_step = elapsed / args.steps * 1e3
     result = {
@@ -397,71 +500,24 @@ def main():
                                 % (config_label(args.tiles, world, sp), ARCH, args.tiles)),
                    "tiles_per_slide": args.tiles, "slides_per_gpu": (1.0 / world) if sp else 1,
                    "parallelism": ("dp%d-lpt" % world) if mixed else ("sp%d" % world) if sp else ("replica x%d" % world)},
-        "roofline": {"bound": "mfma", "kernel": "gp_dilated_attn_fwd", "achieved": round(achieved, 2),
-                     "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
-                     "traffic": traffic, "flops_per_launch": att_flops_launch, "avg_launch_ms": round(avg_att_s * 1e3, 4),
-                     "launches": n_att},
-        "attn_mfma_util_pct": round(100 * achieved / PEAK_BF16_TFLOPS, 2),
-        "merge_roofline": {"bound": "hbm", "kernel": "gp_branch_merge_ln", "achieved": round(merge_gbs, 1),
-                           "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(merge_gbs / PEAK_HBM_GBS, 4),
-                           "traffic": pmc_traffic(args.tiles, "branch_merge_v3_kernel<5") if plain else None,
-                           "bytes_per_launch": merge_bytes},
         "model_tflops": round(total_tf * args.steps * (1 if (sp or mixed) else world) / elapsed, 2),
-        "kernel_ms_per_step": {k: round(v[1] / args.timing_steps, 3) for k, v in sorted(kt.items())},
         "launch": "hip-graph replay" if model.use_hip_graphs else "eager",
     }
     if sp:
         result["sp_exchange_mb_per_layer_rank0"] = round(model._sp.plan.exchange_bytes(0) / 1e6, 1)
-        # the SP gather (gp_dilated_sparsify_dests): per branch that crosses a cut, read the K and V
-        # head-group columns of this rank's tokens (2*C_b bf16 each) and write one row per destination
-        # chunk (transfer-free branches are read in place by the attention: no sparsify bytes)
-        plan = model._sp.plan
-        a_w, b_w = plan.bounds[rank]
-        sp_bytes = sum((b_w - a_w) * 2 * plan.C[b] * 2 + sum(plan.send_splits(rank, b)) * 2 * plan.C[b] * 2
-                       for b in range(len(plan.C)) if not plan.no_xfer[b])
-        n_sp, ms_sp = kt.get("sparsify", (0, 0.0))
-        sp_gbs = sp_bytes / (ms_sp / max(n_sp, 1) / 1e3) / 1e9 if ms_sp > 0 else 0.0
-        result["sparsify_roofline"] = {"bound": "hbm", "kernel": "gp_dilated_sparsify_dests",
-                                       "achieved": round(sp_gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                                       "frac": round(sp_gbs / PEAK_HBM_GBS, 4), "traffic": None,
-                                       "bytes_per_launch": sp_bytes}
-        # every rank's view (shard, xGMI bytes, exposed exchange wait, kernel rooflines), gathered
-        mine_rep = sp_rank_report(model, kt, rank, args.timing_steps, L, segs, ratios, monitor)
-        reps = [None] * world
-        dist.all_gather_object(reps, mine_rep)
-        result["sp_ranks"] = reps
-        result["sp_exchange_exposed_ms_per_layer_max"] = max(
-            r["exchange_exposed"]["ms_per_layer"] for r in reps)
         result["sp_transport"] = "rccl" if backend == "nccl" else backend + " (host-staged rehearsal)"
-    if world == 1 and plain and args.tiles == 70000 and not args.no_c4_ref:
-        # the C4 256k slide on this one GPU, same process: the N > 1 lines shard THIS workload, so their
-        # speedup over this line (not over the 70k `value`) is the sequence-parallel scaling
-        x4, c4 = make_slide(256000, seed=1)
-        x4t, c4t = torch.from_numpy(x4).to(dev), torch.from_numpy(c4).to(dev)
-        del x4, c4
-        print("bench: C4 256k reference line on this GPU ...", file=sys.stderr, flush=True)
-        with torch.no_grad():
-            for _ in range(2):
-                model(x4t, c4t, all_layer_embed=True)
-            torch.cuda.synchronize(dev)
-            t0 = time.perf_counter()
-            for _ in range(3):
-                model(x4t, c4t, all_layer_embed=True)
-            torch.cuda.synchronize(dev)
-            e4 = time.perf_counter() - t0
-        result["c4_256k_same_gpu"] = {
-            "workload": "C4 slide (256,000 tiles) forward on this one GPU, all_layer_embed=True, HIP-graph replay",
-            "tiles_per_s": round(256000 * 3 / e4, 2), "ms_per_step": round(e4 / 3 * 1e3, 3), "steps": 3,
-            "note": "the N > 1 lines shard this workload: their speedup over this line is the C4 scaling"}
-        del x4t, c4t
-    if rank == 0 and not args.no_cpu_baseline:
-        threads, usable, ncpu, _ = host_cores()
-        threads = args.cpu_threads or threads
-        print("bench: CPU baseline on %d threads ..." % threads, file=sys.stderr, flush=True)
-        result["cpu_baseline"] = cpu_baseline(args.tiles, threads, total_tflops=total_tf)
-        if world == 1 and not mixed and not args.no_cpu_full:
-            print("bench: CPU full forwards (C1, C2) ...", file=sys.stderr, flush=True)
-            result["cpu_full_forwards"] = cpu_full_forwards([("C1", 1024), ("C2", 16384)], threads)
+    if args.full:                   # everything beyond the headline figure, each a run of its own
+        result.update(kernel_report(args, model, rank, world, sp, mixed, sizes if mixed else None, monitor, L,
+                                    segs, ratios))
+        if world == 1 and plain and args.tiles == 70000 and not args.no_c4_ref:
+            result["c4_256k_same_gpu"] = c4_same_gpu(model, dev)
+        if rank == 0 and not args.no_cpu_baseline:
+            threads = args.cpu_threads or host_cores()[0]
+            print("bench: CPU baseline on %d threads ..." % threads, file=sys.stderr, flush=True)
+            result["cpu_baseline"] = cpu_baseline(args.tiles, threads, total_tflops=total_tf)
+            if world == 1 and not mixed and not args.no_cpu_full:
+                print("bench: CPU full forwards (C1, C2) ...", file=sys.stderr, flush=True)
+                result["cpu_full_forwards"] = cpu_full_forwards([("C1", 1024), ("C2", 16384)], threads)
     if rank == 0:
         print(json.dumps(result), flush=True)
     if monitor is not None:

@@ -6,7 +6,7 @@ TAG=${1:-r05_base}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-timeout -k 10 300 python bench.py --no-cpu-baseline --no-c4-ref > $OUT/bench_70k.json 2> $OUT/bench_70k.err
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-c4-ref > $OUT/bench_70k.json 2> $OUT/bench_70k.err
 rc=$?; echo "bench70k rc=$rc"; cut -c1-400 $OUT/bench_70k.json; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python bench.py --no-cpu-baseline --no-c4-ref > $OUT/prof.log 2>&1
 rc=$?; echo "rocprof rc=$rc"; [ $rc -eq 0 ] || exit $rc

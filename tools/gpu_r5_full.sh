@@ -12,7 +12,7 @@ rc=$?; echo "pytest rc=$rc"; tail -3 $OUT/pytest_gpu.log; cp gpurun_out/parity_m
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
 rc=$?; echo "smoke rc=$rc"; tail -1 $OUT/smoke.log; [ $rc -eq 0 ] || exit $rc
 fi
-timeout -k 10 300 python bench.py --no-cpu-baseline > $OUT/bench_70k.json 2> $OUT/bench_70k.err
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > $OUT/bench_70k.json 2> $OUT/bench_70k.err
 rc=$?; echo "bench70k rc=$rc"; cut -c1-300 $OUT/bench_70k.json; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python bench.py --no-cpu-baseline --no-c4-ref > $OUT/prof.log 2>&1
 rc=$?; echo "rocprof rc=$rc"; [ $rc -eq 0 ] || exit $rc

@@ -5,7 +5,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 GP_BENCH_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node $W \
-    --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus $W --steps 2 --warmup 1 --tiles $TILES \
+    --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus $W --steps 2 --warmup 1 --tiles $TILES \
     > $OUT/bench_sp$W.json 2> $OUT/bench_sp$W.err
 rc=$?; echo "sp bench rc=$rc"; cat $OUT/bench_sp$W.json; [ $rc -eq 0 ] || tail -30 $OUT/bench_sp$W.err
 exit $rc

@@ -12,7 +12,7 @@ echo "list rc=$?"
 pass() {
   name=$1; shift
   timeout -s KILL 150 rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -o run -- \
-      python bench.py --no-cpu-baseline --steps 1 --warmup 1 --timing-steps 1 $BENCH_ARGS > $OUT/$name.log 2>&1
+      python bench.py --full --no-cpu-baseline --steps 1 --warmup 1 --timing-steps 1 $BENCH_ARGS > $OUT/$name.log 2>&1
   rc=$?; echo "pass $name rc=$rc"; return $rc
 }
 BENCH_ARGS="$*"
