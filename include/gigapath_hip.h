@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GP_ABI_VERSION 10
+#define GP_ABI_VERSION 11
 #define GP_EARG (-1)
 #define GP_MAX_BRANCHES 8
 #define GP_MAX_DESTS 8
@@ -238,6 +238,36 @@ int gp_dilated_attn_fwd_varlen(const void* plan_host, const void* plan_dev, int 
                                int fmt, void* stream);
 int gp_branch_merge_ln_varlen(const void* plan_host, const void* plan_dev, const float* ln_w,
                               const float* ln_b, float eps, uint16_t* out, int fmt, void* stream);
+
+/* ---- The CLS row of the last layer's attention (ABI 11).  With global_pool off the slide readout
+ * (slide_encoder.py:213-221, outcome = self.norm(x)[:, 0]) reads one row per slide from each layer, so
+ * the last layer's DilatedAttention.forward (dilated_attention.py:133-217) is needed for the CLS token
+ * only: for each of nslide slides, out[i, :] = inner_attn_ln(merge(branches))[token 0], straight from the
+ * fused q | k | v buffer (q / k / v / row_stride as gp_dilated_attn_fwd).
+ * slide_off / slide_len: [nslide] int64 DEVICE arrays, the row of each slide's token 0 and its length L
+ *   (1 <= L <= max_len; a batch [B, L] passes b*L and L, a varlen packing its tok_off and L_i).
+ * max_len (host): upper bound of slide_len, sizes the launch and the workspace.
+ * Per slide and branch (sl, r): s = min(sl, L), m = ceil(s / r), hpg = (H rounded up to r) / r.  The CLS
+ * token is sparse row 0 of segment 0 with phase 0 (dense_to_sparse, dilated_attention.py:16-31), so only
+ * heads h < hpg are covered, and its keys are tokens 0, r, 2r, ..., (m - 1) r: all real, no zero pads.
+ *   covered head: lse = logsumexp_i(q . k_i * scale) (natural log), o = softmax . V, o rounded to act
+ *     (flash_attn's out, multihead_attention.py:97-107); P stays fp32;
+ *   merge (scattering, dilated_attention.py:100-131): an uncovered (branch, head) has o = 0, lse = -1e8;
+ *     lse == 0 -> -1e8 (:46); w = fp32 softmax over ALL nbranch LSEs, out = sum_b w_b o_b in branch order
+ *     (every LSE at -1e8, e.g. L = 1 with q = 0: the uniform average, uncovered zeros included);
+ *   then LayerNorm over H*D in fp32 (skipped if ln_w == NULL), rounded to act.
+ * softmax_scale / q_log2_prescaled / fmt as gp_dilated_attn_fwd (all three fmt values: with
+ * GP_FMT_F16_VBF16 v is read as bf16; out is fp16).  D in {48, 64, 96}, H*D <= 1536, nslide <= 65535.
+ * out: [nslide, H*D] act.  ws: gp_cls_attn_workspace_bytes(...) bytes, 16-byte aligned (host only; -1 on
+ * bad arguments).  Two launches (per-chunk partial softmax of 256 keys, then one workgroup per slide), no
+ * atomics.  Replaces, for that row, gp_dilated_attn_fwd + gp_branch_merge_ln. */
+int64_t gp_cls_attn_workspace_bytes(int64_t max_len, int64_t nslide, int H, int D, const int32_t* seg_len,
+                                    const int32_t* ratios, int nbranch);
+int gp_cls_attn_merge_ln(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t row_stride,
+                         const int64_t* slide_off, const int64_t* slide_len, int64_t nslide, int64_t max_len,
+                         int H, int D, const int32_t* seg_len, const int32_t* ratios, int nbranch,
+                         float softmax_scale, int q_log2_prescaled, int fmt, const float* ln_w,
+                         const float* ln_b, float eps, uint16_t* out, void* ws, int64_t ws_bytes, void* stream);
 
 /* Residual add fused with the next pre-LN (encoder.py:141,147 / :159,126):
  *   x += y + bias (fp32 residual stream, in place);  ln_out = LayerNorm(x) (skipped if ln_w == NULL).

@@ -15,7 +15,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "_lib", "libgigapath_hip.so")
-ABI_VERSION = 10
+ABI_VERSION = 11
 MAX_BRANCHES = 8
 MAX_DESTS = 8
 
@@ -56,6 +56,9 @@ SIGNATURES = {
     "gp_seg_attn_fwd_f16": [c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp],
     "gp_branch_merge_ln": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_i32,
                            c_vp],
+    "gp_cls_attn_workspace_bytes": [c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32],
+    "gp_cls_attn_merge_ln": [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_f32,
+                             c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp, c_i64, c_vp],
     "gp_residual_layernorm": [c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_i64, c_i32, c_i32, c_vp],
     "gp_residual2_layernorm": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_i64, c_i32, c_i32, c_vp],
     "gp_gelu_layernorm": [c_vp, c_vp, c_vp, c_f32, c_vp, c_i64, c_i32, c_i32, c_vp],
@@ -79,7 +82,8 @@ SIGNATURES = {
     "gp_ffn_fc2_ln_resid": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64,
                             c_vp, c_f32, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i32, c_vp],
 }
-_RESTYPES = {"gp_last_error_string": ctypes.c_char_p, "gp_varlen_plan_bytes": c_i64, "gp_gemm_workspace_bytes": c_i64}
+_RESTYPES = {"gp_last_error_string": ctypes.c_char_p, "gp_varlen_plan_bytes": c_i64, "gp_gemm_workspace_bytes": c_i64,
+             "gp_cls_attn_workspace_bytes": c_i64}
 
 _lib = None
 
@@ -339,6 +343,37 @@ def branch_merge_ln(outs, lses, segs, ratios, B, L, H, D, ln_w, ln_b, eps, out):
     _check(lib.gp_branch_merge_ln(_ptr_array(outs), _ptr_array(lses), _i32_array(segs), _i32_array(ratios),
                                   len(segs), B, L, H, D, _ptr(ln_w), _ptr(ln_b), eps, _ptr(out), fmt, _stream()),
            "gp_branch_merge_ln")
+
+
+def cls_attn_workspace_bytes(max_len, nslide, H, D, segs, ratios) -> int:
+    """Bytes of cls_attn_merge_ln's partials workspace (host only: works without a GPU)."""
+    nb = int(load_library().gp_cls_attn_workspace_bytes(int(max_len), int(nslide), H, D, _i32_array(segs),
+                                                        _i32_array(ratios), len(segs)))
+    if nb < 0:
+        raise ValueError("cls_attn_workspace_bytes: bad shape (max_len %d, nslide %d, H %d, D %d, %d branches)"
+                         % (max_len, nslide, H, D, len(segs)))
+    return nb
+
+
+def cls_attn_merge_ln(q, k, v, row_stride, slide_off, slide_len, max_len, H, D, segs, ratios, ln_w, ln_b, eps, out,
+                      ws, softmax_scale=0.0, q_log2_prescaled=False, v_bf16=False):
+    """out[i] = inner_attn_ln(merge(branches)) of slide i's CLS token (gp_cls_attn_merge_ln): slide_off / slide_len
+    [nslide] int64 device tensors (row of token 0, length <= max_len); out [nslide, H*D] in q's format; ws: a
+    uint8 tensor of cls_attn_workspace_bytes(...).  v_bf16: as dilated_attn_fwd."""
+    lib = load_library()
+    fmt = qkv_fmt_of(q.dtype, v_bf16)
+    for t in (q, k, v):
+        if not t.is_cuda or t.dtype != q.dtype:
+            raise TypeError("q/k/v must be device tensors of one 16-bit dtype")
+    _dev(slide_off, torch.int64, "slide_off"); _dev(slide_len, torch.int64, "slide_len")
+    n = slide_off.numel()
+    if slide_len.numel() != n or out.numel() != n * H * D:
+        raise ValueError("cls_attn_merge_ln: slide_off, slide_len and out [nslide, H*D] disagree on nslide")
+    _dev(out, q.dtype, "out"); _dev(ws, torch.uint8, "ws")
+    _check(lib.gp_cls_attn_merge_ln(_ptr(q), _ptr(k), _ptr(v), row_stride, _ptr(slide_off), _ptr(slide_len), n,
+                                    int(max_len), H, D, _i32_array(segs), _i32_array(ratios), len(segs),
+                                    float(softmax_scale), int(bool(q_log2_prescaled)), fmt, _ptr(ln_w), _ptr(ln_b),
+                                    eps, _ptr(out), _ptr(ws), ws.numel(), _stream()), "gp_cls_attn_merge_ln")
 
 
 def residual_layernorm(x, y, bias, ln_w, ln_b, eps, ln_out, rows, cols):

@@ -26,9 +26,14 @@ DilatedAttention.forward (component/dilated_attention.py:133-217) and the FFN
 GEMM operands are 16-bit (bf16, or fp16 under the caller's fp16 autocast) with fp32 accumulation.  Weights are packed once per parameter
 version (fused QKV weight, bf16 GEMM operands, fp32 norms/biases) and workspaces are reused
 across calls of the same shape.  No CPU fallback exists: every non-GEMM op is a HIP kernel.
+
+When the caller reads only the CLS row of each slide (LongNetViT with global_pool off), the last layer runs its
+QKV GEMM in full and the rest for those rows alone (cls_tail: gp_cls_attn_merge_ln, then the same entry points
+at M = slides).
 """
 from __future__ import annotations
 
+import contextlib
 import functools
 import math
 import os
@@ -477,20 +482,23 @@ def fused_post_attention(pl: "PackedLayer", nxt: Optional["PackedLayer"], ws):
 
 
 def ffn_forward(pl: "PackedLayer", a: torch.Tensor, f: torch.Tensor, y: torch.Tensor, fstats, gemm_ws,
-                M: int, F: int) -> Optional[torch.Tensor]:
+                M: int, F: int, timed: bool = True) -> Optional[torch.Tensor]:
     """FeedForwardNetwork.forward (feedforward_network.py:131-142) without its residual: y = FFN(a).
-    Returns the bias the residual add still owes (b2 on the unfused path, None when fused)."""
+    Returns the bias the residual add still owes (b2 on the unfused path, None when fused).
+    timed=False: no TIMER spans of its own (the CLS tail's M = n launches are timed as one cls_tail span and
+    must not be counted among the full-size gemm_fc1 / gemm_fc2 launches)."""
+    span = TIMER.span if timed else (lambda name: contextlib.nullcontext())
     if pl.ffn_fused and fstats is not None:
-        with TIMER.span("gemm_fc1"):
+        with span("gemm_fc1"):
             _hip.ffn_fc1_gelu(a, pl.w1, pl.b1_f32, f, fstats)
-        with TIMER.span("gemm_fc2"):
+        with span("gemm_fc2"):
             _hip.ffn_fc2_ln(f, pl.w2g, fstats, pl.c2, pl.d2, pl.fln_eps, y, gemm_ws)
         return None
-    with TIMER.span("gemm_fc1"), blaslt_serialized():
+    with span("gemm_fc1"), blaslt_serialized():
         torch.addmm(pl.b1, a, pl.w1.t(), out=f)
-    with TIMER.span("gelu_ln"):
+    with span("gelu_ln"):
         _hip.gelu_layernorm(f, pl.fln_w, pl.fln_b, pl.fln_eps, f, M, F)
-    with TIMER.span("gemm_fc2"), blaslt_serialized():
+    with span("gemm_fc2"), blaslt_serialized():
         torch.mm(f, pl.w2.t(), out=y)
     return pl.b2
 
@@ -567,7 +575,45 @@ def dilated_attention_core(pa: PackedAttention, qkv: torch.Tensor, B: int, L: in
 # ------------------------------------------------------------------------------------------
 # encoder engine
 # ------------------------------------------------------------------------------------------
+class ClsRows:
+    """Buffers of the last layer's CLS tail (EncoderEngine.run_layers cls_rows=): n = one row per slide.
+    off / len: [n] int64 device tensors, the row of each slide's token 0 in the workspace and its length
+    (gp_cls_attn_merge_ln's slide_off / slide_len; also the gather index of the CLS rows of ws.x).  They and
+    every buffer here live as long as the workspace that owns them: a HIP graph bakes their pointers."""
+
+    def __init__(self, dev, offs: Sequence[int], lens: Sequence[int], E: int, F: int, H: int, segs, ratios,
+                 act: torch.dtype):
+        n = len(offs)
+        self.n, self.max_len = n, int(max(lens))
+        self.off = torch.tensor([int(o) for o in offs], dtype=torch.int64, device=dev)
+        self.len = torch.tensor([int(l) for l in lens], dtype=torch.int64, device=dev)
+        self.x = torch.empty(n, E, dtype=torch.float32, device=dev)      # the CLS rows of the residual stream
+        self.a = torch.empty(n, E, dtype=act, device=dev)                # inner_attn_ln(merge), then LN2(x1)
+        self.y = torch.empty(n, E, dtype=act, device=dev)                # out-proj output
+        self.y2 = torch.empty(n, E, dtype=act, device=dev)               # fc2 output
+        self.f = torch.empty(n, F, dtype=act, device=dev)
+        self.fstats, self.gemm_ws = ffn_buffers(dev, n, E, F)
+        self.attn_ws = torch.empty(_hip.cls_attn_workspace_bytes(self.max_len, n, H, E // H, segs, ratios),
+                                   dtype=torch.uint8, device=dev)
+
+
 class Workspace:
+    cls: Optional[ClsRows] = None
+
+    def cls_rows(self) -> ClsRows:
+        """The CLS tail's buffers, allocated on first use (an eager run precedes every graph capture)."""
+        if self.cls is None:
+            dev, E, F = self.x.device, self.x.shape[1], self.f.shape[1]
+            segs, ratios, act = self.key[-3], self.key[-2], self.key[-1]
+            H = self.key[-4]
+            offs, lens = self._slides()
+            self.cls = ClsRows(dev, offs, lens, E, F, H, segs, ratios, act)
+        return self.cls
+
+    def _slides(self):
+        B, L = self.key[1], self.key[2]
+        return [b * L for b in range(B)], [L] * B
+
     def __init__(self, dev, B: int, L: int, E: int, F: int, H: int, segs, ratios, act: torch.dtype = torch.bfloat16):
         M = B * L
         self.key = (str(dev), B, L, E, F, H, tuple(segs), tuple(ratios), act)
@@ -605,6 +651,9 @@ class PackedWorkspace(Workspace):
         self.attn = VarlenScratch(dev, self.Ls, H, E // H, segs, ratios, self.qkv)
         self.tok_off = self.attn.plan.tok_off
         self.cls_idx = torch.tensor(self.tok_off[:-1], dtype=torch.int64, device=dev)
+
+    def _slides(self):
+        return self.tok_off[:-1], self.Ls
 
 
 class EncoderEngine:
@@ -691,10 +740,14 @@ class EncoderEngine:
         if self.pws is ws:
             self.pws = None
 
-    def run_layers(self, ws: Workspace, B: int, L: int, layer_hook=None, shift_ready: bool = False):
+    def run_layers(self, ws: Workspace, B: int, L: int, layer_hook=None, shift_ready: bool = False,
+                   cls_rows: Optional[ClsRows] = None):
         """ws.x holds the fp32 embedding and ws.a = LN1_0(ws.x) (16-bit).  Runs every layer in
         place; layer_hook(i) is called after layer i-1 finishes (i = 1..depth).  shift_ready: ws.shift[0]
-        already holds the row means of ws.x (gp_posembed_cls_ln's row_mean); otherwise they are computed."""
+        already holds the row means of ws.x (gp_posembed_cls_ln's row_mean); otherwise they are computed.
+        cls_rows (ws.cls_rows()): the caller reads only the CLS row of each slide from the LAST layer's
+        output, so that layer runs its QKV GEMM and then cls_tail() on one row per slide; its output is
+        cls_rows.x, and ws.x keeps the second-to-last layer's.  None: every layer in full."""
         M = B * L
         E = ws.x.shape[1]
         F = ws.f.shape[1]
@@ -709,8 +762,11 @@ class EncoderEngine:
                         linear(ws.a, pa.w_qkv, pa.b_qkv, pa.b_qkv_f32, ws.qkv, ws.gemm_ws, v_bf16=pa.v_bf16)
                     else:
                         fused_qkv(pl, ws, ws.qkv)
-                dilated_attention_core(pa, ws.qkv, B, L, ws.attn, ws.a, v_bf16=pa.v_bf16)
-                fused_post_attention(pl, self.layers[li + 1] if li + 1 < nl else None, ws)
+                if cls_rows is not None and li + 1 == nl:
+                    cls_tail(pl, ws, cls_rows)
+                else:
+                    dilated_attention_core(pa, ws.qkv, B, L, ws.attn, ws.a, v_bf16=pa.v_bf16)
+                    fused_post_attention(pl, self.layers[li + 1] if li + 1 < nl else None, ws)
                 if layer_hook is not None:
                     layer_hook(li + 1)
             return
@@ -718,6 +774,11 @@ class EncoderEngine:
             pa = pl.attn
             with TIMER.span("gemm_qkv"):
                 linear(ws.a, pa.w_qkv, pa.b_qkv, pa.b_qkv_f32, ws.qkv, ws.gemm_ws, v_bf16=pa.v_bf16)
+            if cls_rows is not None and li + 1 == nl:
+                cls_tail(pl, ws, cls_rows)
+                if layer_hook is not None:
+                    layer_hook(li + 1)
+                continue
             dilated_attention_core(pa, ws.qkv, B, L, ws.attn, ws.a, v_bf16=pa.v_bf16)
             with TIMER.span("gemm_out"):
                 linear(ws.a, pa.w_o, None, None, ws.y, ws.gemm_ws)
@@ -750,6 +811,31 @@ def residual_pair(pl: "PackedLayer", nxt: Optional["PackedLayer"], ws, M: int, E
     b2 = ffn_forward(pl, ws.a, ws.f, ws.y, ws.fstats, ws.gemm_ws, M, F)
     with TIMER.span("resid_ln"):
         _hip.residual_layernorm(ws.x, ws.y, b2, ln1[0], ln1[1], ln1[2], ws.a, M, E)
+
+
+# the last layer for the CLS rows only (cls_tail) when the readout is the CLS token (LongNetViT with
+# global_pool off).  =0 restores the full last layer (A/B runs, tests/test_gpu_cls_tail.py).
+CLS_TAIL = os.environ.get("GIGAPATH_CLS_TAIL", "1") != "0"
+
+
+def cls_tail(pl: "PackedLayer", ws, c: ClsRows):
+    """The last encoder layer after its QKV GEMM wrote ws.qkv, for the CLS token of every slide: the row the
+    readout outcome = self.norm(x)[:, 0] (slide_encoder.py:213-221) takes from that layer.  The CLS query's
+    attention, branch merge and inner LN in gp_cls_attn_merge_ln (K / V of every token it attends to come from
+    ws.qkv), then EncoderLayer.forward's remaining steps (encoder.py:141-162) at M = n rows on c's buffers:
+    out-proj, residual + LN2, FFN, residual.  Result: c.x [n, E] fp32."""
+    pa = pl.attn
+    n, E, F = c.n, pa.E, c.f.shape[1]
+    q, k, v = ws.qkv, ws.qkv[:, E:], ws.qkv[:, 2 * E:]
+    with TIMER.span("cls_attn"):
+        _hip.cls_attn_merge_ln(q, k, v, 3 * E, c.off, c.len, c.max_len, pa.H, pa.D, pa.segs, pa.ratios, pa.ln_w,
+                               pa.ln_b, pa.ln_eps, c.a, c.attn_ws, 0.0, pa.prescaled, v_bf16=pa.v_bf16)
+    with TIMER.span("cls_tail"):
+        torch.index_select(ws.x, 0, c.off, out=c.x)
+        linear(c.a, pa.w_o, None, None, c.y, c.gemm_ws)
+        _hip.residual2_layernorm(c.x, c.y, pa.b_o, None, None, pl.ln2_w, pl.ln2_b, pl.ln2_eps, c.a, n, E)
+        b2 = ffn_forward(pl, c.a, c.f, c.y2, c.fstats, c.gemm_ws, n, F, timed=False)
+        _hip.residual2_layernorm(c.x, c.y, pa.b_o, c.y2, b2, None, None, 1e-5, c.a, n, E)
 
 
 def gemm_flops(B: int, N: int, E: int, F: int, C: int, depth: int) -> float:

@@ -275,8 +275,8 @@ class LongNetViT(nn.Module):
         self._packed_top(dev)
         self.encoder.engine.pack(self.encoder, dev)
         key = (str(dev), int(torch.cuda.current_stream(dev).cuda_stream), tuple(x.shape), x.dtype, c.dtype,
-               runtime.act_dtype(), bool(all_layer_embed), bool(self.global_pool), self._top_sig,
-               self.encoder.engine._sig)
+               runtime.act_dtype(), bool(all_layer_embed), bool(self.global_pool), bool(runtime.CLS_TAIL),
+               self._top_sig, self.encoder.engine._sig)
         ent = self._graph_lookup(key)
         if ent is None and self._graph_wanted(key):
             ent = self._capture(key, x, c, lambda sx, sc: self._forward_device(sx, sc, all_layer_embed, False),
@@ -434,7 +434,7 @@ class LongNetViT(nn.Module):
             self.encoder.engine.pack(self.encoder, dev)
             key = ("packed", str(dev), int(torch.cuda.current_stream(dev).cuda_stream), Ns, x_cat.dtype,
                    c_cat.dtype, runtime.act_dtype(), bool(all_layer_embed), bool(self.global_pool),
-                   self._top_sig, self.encoder.engine._sig)
+                   bool(runtime.CLS_TAIL), self._top_sig, self.encoder.engine._sig)
             ent = self._graph_lookup(key)
             if ent is None and self._graph_wanted(key):
                 ent = self._capture(key, x_cat, c_cat,
@@ -481,25 +481,30 @@ class LongNetViT(nn.Module):
         n_out = (1 + len(layers)) if all_layer_embed else 1
         res = torch.empty(n_out, S, E, dtype=torch.float32, device=dev)
         pool = torch.empty(S, E, dtype=torch.float32, device=dev)
+        # only the CLS rows are read: the last layer runs for them alone and leaves them in cls.x
+        cls = ws.cls_rows() if (runtime.CLS_TAIL and not self.global_pool) else None
 
         def readout(slot: int):
             if self.global_pool:
                 for i, L in enumerate(Ls):
                     t0 = ws.tok_off[i]
                     _hip.mean_tokens(ws.x[t0:t0 + L], 1, L, E, 1, pool[i:i + 1])
+            elif cls is not None and slot == len(layers):
+                _hip.layernorm_f32(cls.x, E, top["norm_w"], top["norm_b"], top["norm_eps"], res[slot], S, E)
+                return
             else:
                 torch.index_select(ws.x, 0, ws.cls_idx, out=pool)
             _hip.layernorm_f32(pool, E, top["norm_w"], top["norm_b"], top["norm_eps"], res[slot], S, E)
 
         if all_layer_embed:
             readout(0)
-        eng.run_layers(ws, 1, T, readout if all_layer_embed else None, shift_ready=True)
+        eng.run_layers(ws, 1, T, readout if all_layer_embed else None, shift_ready=True, cls_rows=cls)
         if not all_layer_embed:
             if self.global_pool:
                 _hip.layernorm_f32(ws.x, E, top["enc_w"], top["enc_b"], top["enc_eps"], ws.x, T, E)
                 readout(0)
             else:
-                cls_rows = torch.index_select(ws.x, 0, ws.cls_idx)
+                cls_rows = cls.x.clone() if cls is not None else torch.index_select(ws.x, 0, ws.cls_idx)
                 _hip.layernorm_f32(cls_rows, E, top["enc_w"], top["enc_b"], top["enc_eps"], cls_rows, S, E)
                 _hip.layernorm_f32(cls_rows, E, top["norm_w"], top["norm_b"], top["norm_eps"], res[0], S, E)
         return res
@@ -534,24 +539,30 @@ class LongNetViT(nn.Module):
         n_out = (1 + len(layers)) if all_layer_embed else 1
         res = torch.empty(n_out, B, E, dtype=torch.float32, device=dev)
         pool = torch.empty(B, E, dtype=torch.float32, device=dev) if self.global_pool else None
+        # only the CLS rows are read (outcome = self.norm(x)[:, 0], reference :221): the last layer runs for
+        # them alone (runtime.cls_tail) and leaves them in cls.x [B, E]; global_pool reads every row
+        cls = ws.cls_rows() if (runtime.CLS_TAIL and not self.global_pool) else None
 
         def readout(slot: int):
             if self.global_pool:
                 _hip.mean_tokens(ws.x, B, L, E, 1, pool)
                 _hip.layernorm_f32(pool, E, top["norm_w"], top["norm_b"], top["norm_eps"], res[slot], B, E)
+            elif cls is not None and slot == len(layers):
+                _hip.layernorm_f32(cls.x, E, top["norm_w"], top["norm_b"], top["norm_eps"], res[slot], B, E)
             else:
                 _hip.layernorm_f32(ws.x, L * E, top["norm_w"], top["norm_b"], top["norm_eps"], res[slot], B, E)
 
         if all_layer_embed:
             readout(0)
-        eng.run_layers(ws, B, L, readout if all_layer_embed else None, shift_ready=True)
+        eng.run_layers(ws, B, L, readout if all_layer_embed else None, shift_ready=True, cls_rows=cls)
         if not all_layer_embed:
             if self.global_pool:
                 _hip.layernorm_f32(ws.x, E, top["enc_w"], top["enc_b"], top["enc_eps"], ws.x, M, E)
                 readout(0)
             else:
                 cls_rows = torch.empty(B, E, dtype=torch.float32, device=dev)
-                _hip.layernorm_f32(ws.x, L * E, top["enc_w"], top["enc_b"], top["enc_eps"], cls_rows, B, E)
+                src, stride = (cls.x, E) if cls is not None else (ws.x, L * E)
+                _hip.layernorm_f32(src, stride, top["enc_w"], top["enc_b"], top["enc_eps"], cls_rows, B, E)
                 _hip.layernorm_f32(cls_rows, E, top["norm_w"], top["norm_b"], top["norm_eps"], res[0], B, E)
         out_dtype = self.norm.weight.dtype
         return [res[i].to(out_dtype) for i in range(n_out)]
