@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GP_ABI_VERSION 11
+#define GP_ABI_VERSION 12
 #define GP_EARG (-1)
 #define GP_MAX_BRANCHES 8
 #define GP_MAX_DESTS 8
@@ -212,6 +212,38 @@ int gp_branch_merge_ln_window(const uint16_t* const* o_in, const float* const* l
                               int64_t L, int64_t tok_lo, int64_t n_tok, int H, int D, const float* ln_w,
                               const float* ln_b, float eps, uint16_t* out, int fmt, void* stream);
 
+/* ---- Attention for listed query rows (ABI 12): gp_dilated_attn_fwd's product kernel pair (D = 48, pre-scaled q;
+ * fmt GP_FMT_BF16 or GP_FMT_F16_VBF16) run only for the sparse rows a caller lists, for consumers that read the
+ * merge of a few tokens (gp_branch_merge_ln_rows).  A work item is (branch, segment, head, block of 256
+ * list slots); the K / V tile loop is that of the full launch and o / lse of a listed row land at the addresses
+ * the full launch writes with the same bits; unlisted rows are not written.
+ * Lists, per branch b (sl, r; s = min(sl, L), m = ceil(s / r), nseg = ceil(L / s)): for segment n and head group
+ * j the ascending sparse rows i (0 <= i < m) wanted of every head of that group -- the row whose merge slot is
+ * token n m r + i r + j.  grp_off[b]: HOST int32 [nseg r + 1] offsets, group (n, j) at index n r + j; grp_rows[b]:
+ * DEVICE int32 array of the concatenated lists (one set of lists for all B batches; must outlive the launches).
+ * gp_attn_rows_plan_bytes: size of the host plan buffer (-1 on bad arguments).  gp_attn_rows_plan fills it (q / k /
+ * v / o_out / lse_out as gp_dilated_attn_fwd, device pointers not dereferenced);
+ * the caller copies the bytes to a 16-byte aligned device buffer (plan_dev) that stays alive while launches use
+ * it.  One launch (plus the fixup pass) covers every branch, entries ordered by keys per item, longest first. */
+int64_t gp_attn_rows_plan_bytes(int64_t B, int64_t L, const int32_t* seg_len, const int32_t* ratios, int nbranch);
+int gp_attn_rows_plan(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t row_stride, int64_t B,
+                      int64_t L, int H, int D, const int32_t* seg_len, const int32_t* ratios, int nbranch,
+                      const int32_t* const* grp_off, const int32_t* const* grp_rows, uint16_t* const* o_out,
+                      float* const* lse_out, void* plan_host, int64_t plan_bytes);
+int gp_dilated_attn_fwd_rows(const void* plan_host, const void* plan_dev, int q_log2_prescaled, int fmt,
+                             void* stream);
+
+/* gp_branch_merge_ln for a list of tokens (ABI 12): out row b*n_rows + k is the merge (+ inner LN) of token
+ * rows[k] of batch b, bit-identical to row b*L + rows[k] of gp_branch_merge_ln's output.  rows: [n_rows] int32
+ * DEVICE array of tokens in [0, L) (any order; one list for every batch).  out: [B*n_rows, H*D] act, 16-byte
+ * aligned.  H = 16, D = 48, nbranch = 5 only (gp_branch_merge_ln_rows_supported, host only).  With ln_w == NULL
+ * nothing but the branch buffers and the list is read. */
+int gp_branch_merge_ln_rows_supported(int H, int D, int nbranch);
+int gp_branch_merge_ln_rows(const uint16_t* const* o_in, const float* const* lse_in,
+                            const int32_t* seg_len, const int32_t* ratios, int nbranch, int64_t B, int64_t L,
+                            const int32_t* rows, int64_t n_rows, int H, int D, const float* ln_w,
+                            const float* ln_b, float eps, uint16_t* out, int fmt, void* stream);
+
 /* ---- Varlen packing (config C5, SURVEY §8e: "concatenate slides with per-slide segment
  * tables, no cross-slide attention").  nslide slides packed token-major in one qkv buffer
  * [T, qkv_row_stride] (slide i at rows [tok_off[i], tok_off[i] + L[i]), q | k | v at columns
@@ -268,6 +300,19 @@ int gp_cls_attn_merge_ln(const uint16_t* q, const uint16_t* k, const uint16_t* v
                          int H, int D, const int32_t* seg_len, const int32_t* ratios, int nbranch,
                          float softmax_scale, int q_log2_prescaled, int fmt, const float* ln_w,
                          const float* ln_b, float eps, uint16_t* out, void* ws, int64_t ws_bytes, void* stream);
+
+/* gp_cls_attn_merge_ln on compact q | k | v rows (ABI 12): the buffer holds only map_rows rows per slide, token t
+ * of a slide at row slide_off[i] + row_map[t] (row_map: [max_len] int32 DEVICE array, one map for every slide;
+ * slide_off[i] is the slide's first compact row, slide_len[i] still its token count).  Only the entries of the
+ * CLS query's keys (tokens 0, r, ..., (m - 1) r of every branch) are read; each must name the row that holds
+ * that token's q | k | v, and token 0 maps to row 0.  row_map == NULL is gp_cls_attn_merge_ln.  Same arithmetic
+ * in the same order, so the same bits as the unmapped call on the scattered buffer. */
+int gp_cls_attn_merge_ln_map(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t row_stride,
+                             const int64_t* slide_off, const int64_t* slide_len, int64_t nslide, int64_t max_len,
+                             const int32_t* row_map, int64_t map_rows, int H, int D, const int32_t* seg_len,
+                             const int32_t* ratios, int nbranch, float softmax_scale, int q_log2_prescaled,
+                             int fmt, const float* ln_w, const float* ln_b, float eps, uint16_t* out, void* ws,
+                             int64_t ws_bytes, void* stream);
 
 /* Residual add fused with the next pre-LN (encoder.py:141,147 / :159,126):
  *   x += y + bias (fp32 residual stream, in place);  ln_out = LayerNorm(x) (skipped if ln_w == NULL).

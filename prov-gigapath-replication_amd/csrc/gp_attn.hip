@@ -117,6 +117,19 @@ struct AttnArgs {
   const AttnBranch* tab;            // varlen: ntab (slide, branch) entries in device memory
   int32_t ntab;
   DivMagic d_H;
+  const struct AttnListEntry* ltab; // query-list launch (kList): ntab entries in device memory
+};
+
+// Query-list launch (gp_dilated_attn_fwd_rows): one entry per (batch, branch, segment, head group) that has
+// listed rows.  Its work items are (covered head, block of QB list slots); slot k of the entry is sparse row
+// rows[k] of the segment.  br: the branch as a launch holds it, with nqb / d_nqb / item_begin of THIS entry.
+struct AttnListEntry {
+  AttnBranch br;
+  const int32_t* rows;   // [count] ascending sparse rows (device)
+  int32_t count;
+  int32_t n, j, bidx;    // segment, head group (phase), batch
+  int32_t h0;            // first covered head = j * hpg
+  int32_t pad;
 };
 
 // Work item -> (branch, batch, segment, head, query-row range).  Rows [i_lo, i_hi) of
@@ -183,6 +196,48 @@ GP_DEV void decode_item_tab(const AttnArgs& a, int item, WorkItem& w, AttnBranch
 #endif
   w.bi = lo;
   decode_core(e, item - (int)e.item_begin, a.H, a.d_H, e.L, 0, e.L, w);
+}
+
+// Query-list launch: entry = (batch, branch, segment, head group), items ordered by entry (longest keys first);
+// binary search on item_begin, the entry by scalar loads (as decode_item_tab), then head and slot block.
+GP_DEV void decode_item_list(const AttnArgs& a, int item, WorkItem& w, AttnBranch& e, int& count,
+                             const int32_t*& rows) {
+  int lo = 0, hi = a.ntab - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if ((int64_t)item >= a.ltab[mid].br.item_begin) lo = mid; else hi = mid - 1;
+  }
+  lo = __builtin_amdgcn_readfirstlane(lo);
+  AttnListEntry le;
+#if defined(__HIP_DEVICE_COMPILE__)
+  static_assert(sizeof(AttnListEntry) % 4 == 0, "");
+  uint32_t words[sizeof(AttnListEntry) / 4];
+  const __attribute__((address_space(4))) uint32_t* src =
+      (const __attribute__((address_space(4))) uint32_t*)(uintptr_t)(a.ltab + lo);
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(AttnListEntry) / 4); ++i) words[i] = src[i];
+  __builtin_memcpy(&le, words, sizeof(AttnListEntry));
+#else
+  le = a.ltab[lo];
+#endif
+  e = le.br;
+  const GpBranch& g = e.g;
+  const int local = item - (int)e.item_begin;
+  const int hq = (int)div_magic((uint32_t)local, e.d_nqb);
+  w.bi = lo;
+  w.qb = local - hq * e.nqb;
+  w.hh = le.h0 + hq;
+  w.bidx = le.bidx;
+  w.n = le.n;
+  w.bn = le.bidx * g.nseg + le.n;
+  w.j = le.j;
+  const int rem = (int)(a.L - (int64_t)w.n * g.s);
+  const int lim = (rem < g.s ? rem : g.s) - w.j;
+  w.c = lim > 0 ? (int)div_magic((uint32_t)(lim + g.r - 1), e.d_r) : 0;
+  w.i_lo = 0;
+  w.i_hi = g.m;
+  count = le.count;
+  rows = le.rows;
 }
 
 constexpr int kWaves = 4;
@@ -535,8 +590,13 @@ constexpr int attn_wps() { return MODE == 0 && NW == 8 ? (kTab ? GP_ATTN_FAST_WP
 // Measured lab variants of this kernel (the 16x16x32 P.V GP_ATTN_PV16, the 3-slot ring GP_ATTN_RING3) build
 // from round 3's source in git (make -C tools/attn_lab r3lab).
 
-template <int D, bool kPre, int MODE, bool kTab, int NW, bool kH, bool kParts = false>
+// kList: the block's queries are QB slots of its entry's row list instead of QB consecutive sparse rows
+// (decode_item_list).  Only where a query's row index i is formed does the kernel differ: the Q-fragment load,
+// the epilogue's stores and the fixup pass's flag tests take i from the list; a slot past the list's end is a
+// row >= rows_needed (no load, no store).  o / lse land where the full launch puts them.
+template <int D, bool kPre, int MODE, bool kTab, int NW, bool kH, bool kParts = false, bool kList = false>
 __device__ __forceinline__ void attn32_item(const AttnArgs& a, const int item_idx) {
+  static_assert(!kList || (!kTab && !kParts && MODE != kModeGen), "query lists: LDS-DMA modes, [B, L] launches");
   static_assert(!kH || D == 48 || MODE == kModeGen, "fp16 LDS-DMA modes: D = 48");
   static_assert(!kParts || (MODE != kModeGen && !kTab), "key parts: LDS-DMA modes, branch launches");
   static_assert(D == 48 || D == 64, "v2 kernel covers D = 48 and 64");
@@ -574,18 +634,27 @@ __device__ __forceinline__ void attn32_item(const AttnArgs& a, const int item_id
   // ---- work item (32-bit index math: items < 2^31, checked on the host)
   WorkItem wi;
   AttnBranch te;                             // kTab: this item's table entry
-  if constexpr (kTab) decode_item_tab(a, item_idx, wi, te);
+  int lcount = 0;                            // kList: the entry's list
+  const int32_t* lrows = nullptr;
+  if constexpr (kList) decode_item_list(a, item_idx, wi, te, lcount, lrows);
+  else if constexpr (kTab) decode_item_tab(a, item_idx, wi, te);
   else decode_item(a, item_idx, wi);
-  const AttnBranch& brr = kTab ? te : a.br[wi.bi];
+  const AttnBranch& brr = (kTab || kList) ? te : a.br[wi.bi];
   const GpBranch g = brr.g;
   const int hh = wi.hh, c = wi.c, bn = wi.bn;
   const int rows_needed = wi.i_hi;
-  const int q0 = wi.i_lo + wi.qb * QB;
-  if (q0 >= rows_needed) return;
+  const int q0 = wi.i_lo + wi.qb * QB;       // kList: the block's first list slot
+  if (q0 >= (kList ? lcount : rows_needed)) return;
+  // kList: sparse row of list slot k; an empty slot, or an entry outside the segment's rows, is rows_needed
+  auto list_row = [&](int k) -> int {
+    const int v = k < lcount ? lrows[k] : rows_needed;
+    return (unsigned)v < (unsigned)rows_needed ? v : rows_needed;
+  };
   // rows >= c are zero-padded queries (their q is 0): load nothing for them
   const int qvalid = c < rows_needed ? c : rows_needed;
   if constexpr (MODE == kModeFix) {          // only blocks the fast kernel flagged are recomputed
-    const int i = q0 + (int)threadIdx.x;
+    const int i = kList ? (threadIdx.x < QB ? list_row(q0 + (int)threadIdx.x) : rows_needed)
+                        : q0 + (int)threadIdx.x;
     bool flagged = false;
     if (threadIdx.x < QB && i < rows_needed)
       flagged = __float_as_uint(brr.lse[((int64_t)wi.bn * a.H + wi.hh) * g.m + i]) == kLseRedo;
@@ -596,7 +665,8 @@ __device__ __forceinline__ void attn32_item(const AttnArgs& a, const int item_id
   // items share its fixup block -- a packed (varlen) slide's rows never depend on a neighbour's overflow
   bool fixrow = true;
   if constexpr (MODE == kModeFix) {
-    const int iq = q0 + (int)(threadIdx.x >> 6) * 32 + (int)(threadIdx.x & 31);
+    const int sq = q0 + (int)(threadIdx.x >> 6) * 32 + (int)(threadIdx.x & 31);
+    const int iq = kList ? list_row(sq) : sq;
     fixrow = iq < rows_needed &&
              __float_as_uint(brr.lse[((int64_t)wi.bn * a.H + wi.hh) * g.m + iq]) == kLseRedo;
   }
@@ -631,8 +701,10 @@ __device__ __forceinline__ void attn32_item(const AttnArgs& a, const int item_id
 
   // Q fragments (B operand): lane holds Q[q = l32][d = 16ks + 8h .. +7]
   bf16x8 qf[KS];
+  int irow = 0;                              // kList: this lane's query row, kept for the epilogue
+  if constexpr (kList) irow = list_row(q0 + w * 32 + l32);
   {
-    const int i = q0 + w * 32 + l32;
+    const int i = kList ? irow : q0 + w * 32 + l32;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       bf16x8 z = {};
@@ -762,7 +834,7 @@ __device__ __forceinline__ void attn32_item(const AttnArgs& a, const int item_id
   // GP_ATTN_SKIP_IDLE: a wave whose 32 queries all lie at or past the last needed row (the tail
   // q-block of a segment) skips the MFMAs and the softmax -- its outputs are never stored -- and
   // only issues its share of the K/V staging and the barriers (~2 % of the wave-tiles at 70k)
-  const bool wact = !GP_ATTN_SKIP_IDLE || __builtin_amdgcn_readfirstlane(q0 + w * 32) < rows_needed;
+  const bool wact = !GP_ATTN_SKIP_IDLE || __builtin_amdgcn_readfirstlane(q0 + w * 32) < (kList ? lcount : rows_needed);
   auto tile_step = [&](int t, auto setc) {
     constexpr int SET = decltype(setc)::value;
     if (t + 1 < t_hi) load_tile((t + 1) * KT, std::integral_constant<int, 1 - SET>());
@@ -1011,7 +1083,7 @@ __device__ __forceinline__ void attn32_item(const AttnArgs& a, const int item_id
     mr = mf;
   }
   const float inv = empty ? 0.f : so / l;
-  const int i = q0 + w * 32 + l32;
+  const int i = kList ? irow : q0 + w * 32 + l32;
   if constexpr (GP_ATTN_WIDE_STORE != 0) {
     // lane (q, h) holds d = 8k + 4h .. +3 for the D/8 groups k.  For each pair of groups (k, k+1)
     // one permlane32_swap per dword gives lanes 0-31 d = 8k .. 8k+7 and lanes 32-63 d = 8k+8 .. 8k+15
@@ -1064,9 +1136,14 @@ __device__ __forceinline__ void attn32_item(const AttnArgs& a, const int item_id
 // (GP_ATTN_FIX_ITEMS): a block reads the lse of every needed row of its kFixItems consecutive items at
 // once (independent loads per lane), exits unless one holds the kLseRedo marker, and recomputes the
 // flagged items in turn; kFixItems = 1 (lab builds) is one item per block in item order.
-template <int D, bool kPre, int MODE, bool kTab = false, int NW = 4, bool kH = false, bool kParts = false>
+// (kList: the fixup pass is one block per item -- a list launch holds few items)
+template <int D, bool kPre, int MODE, bool kTab = false, int NW = 4, bool kH = false, bool kParts = false,
+          bool kList = false>
 __global__ __launch_bounds__(NW * 64, (attn_wps<MODE, kTab, NW>())) void dilated_attn32_kernel(const AttnArgs a) {
-  if constexpr (MODE == kModeFix && kFixItems == 1) {
+  if constexpr (kList) {
+    attn32_item<D, kPre, MODE, kTab, NW, kH, kParts, true>(
+        a, MODE == kModeFix ? (int)blockIdx.x : (int)xcd_group(blockIdx.x, gridDim.x));
+  } else if constexpr (MODE == kModeFix && kFixItems == 1) {
     attn32_item<D, kPre, MODE, kTab, NW, kH, kParts>(a, (int)blockIdx.x);   // its own flagged-row check first
   } else if constexpr (MODE == kModeFix) {
     constexpr int QB = NW * 32;
@@ -1133,6 +1210,8 @@ struct MergeArgs {
   const int64_t* tok_off;
   int32_t nslide;
   DivMagic dnt;        // division by ntok (the batch index of a row)
+  // token list (branch_merge_v3_kernel kList, gp_branch_merge_ln_rows): out row b*ntok + k is token tok_list[k]
+  const int32_t* tok_list;
 };
 
 // One wave per run of kTPW consecutive tokens; lane l owns the EPL = E/64 contiguous elements
@@ -1332,16 +1411,15 @@ __global__ __launch_bounds__(64 * GP_MERGE_WPB) void branch_merge_v2_kernel(cons
   const int h1 = k1h ? h0 : (128 + lane) / 12;
   const int c0 = k1h ? D * h0 + 8 * kq : 8 * lane;
   const int c1 = k1h ? D * h0 + 32 + 4 * kq : 512 + 4 * lane;
-  // LN affine (L1-resident): issued with the branch loads; a null ln_w reads the output row's own
-  // location instead (valid memory, unused) so the registers need no zero-fill
+  // LN affine (L1-resident): issued with the branch loads; nothing is read without an LN (a null ln_w)
   const bool ln = a.ln_w != nullptr;
-  const float* lw = ln ? a.ln_w : reinterpret_cast<const float*>(a.out);
-  const float* lb = ln ? a.ln_b : reinterpret_cast<const float*>(a.out);
-  float w0[8], w1[4], b0[8], b1[4];
-  load_f32<8>(lw + c0, w0);
-  load_f32<4>(lw + c1, w1);
-  load_f32<8>(lb + c0, b0);
-  load_f32<4>(lb + c1, b1);
+  float w0[8] = {}, w1[4] = {}, b0[8] = {}, b1[4] = {};
+  if (ln) {
+    load_f32<8>(a.ln_w + c0, w0);
+    load_f32<4>(a.ln_w + c1, w1);
+    load_f32<8>(a.ln_b + c0, b0);
+    load_f32<4>(a.ln_b + c1, b1);
+  }
   int bidx = 0, p;
   MergeBranch tb[kTab ? GP_MAX_BRANCHES : 1];
   if constexpr (kTab) {
@@ -1490,6 +1568,12 @@ __global__ __launch_bounds__(64 * GP_MERGE_WPB) void branch_merge_v2_kernel(cons
 #endif
 constexpr int kV3Tok = GP_MERGE_V3_TOK;    // most tokens per block (4 waves, up to kV3Tok / 4 tokens each); <= 64
 
+// entry k of the token list, held inside [0, L): a bad list cannot send a load outside the branch buffers
+GP_DEV int list_token(const MergeArgs& a, int k) {
+  const int p = a.tok_list[k];
+  return p < 0 ? 0 : (p < (int)a.L ? p : (int)a.L - 1);
+}
+
 // A MergeBranch table entry by scalar loads (uniform index, constant address space): the entries then live in
 // SGPRs even when the load follows the kernel's global stores (the compiler's uniform-load analysis would
 // otherwise fall back to per-lane loads into VGPRs)
@@ -1509,9 +1593,12 @@ GP_DEV MergeBranch merge_entry_scalar(const MergeBranch* tab, int idx) {
   return e;
 }
 
-template <int NBR, bool kH, bool kTab = false>
+// kList (gp_branch_merge_ln_rows): output row b*ntok + k merges token tok_list[k] of batch b instead of token
+// tok_lo + k -- the only difference, so a listed token's row holds the bits the full merge writes for it.
+template <int NBR, bool kH, bool kTab = false, bool kList = false>
 __global__ __launch_bounds__(256) void branch_merge_v3_kernel(const MergeArgs a, const int tpb) {
 #pragma clang fp contract(off)
+  static_assert(!(kTab && kList), "token list: [B, L] batches only");
   constexpr int E = 768, H = 16, D = 48;
   constexpr int LS = NBR * 16 + 1;           // LDS floats per token (16 per branch entry; +1: bank spread)
   __shared__ float lse_s[kV3Tok * LS];
@@ -1539,7 +1626,7 @@ __global__ __launch_bounds__(256) void branch_merge_v3_kernel(const MergeArgs a,
       const bool live = row < total;
       const int rr = live ? row : total - 1;
       const int bidx = (int)div_magic((uint32_t)rr, a.dnt);
-      const int p = (int)a.tok_lo + (rr - bidx * (int)a.ntok);
+      const int p = kList ? list_token(a, rr - bidx * (int)a.ntok) : (int)a.tok_lo + (rr - bidx * (int)a.ntok);
 #pragma unroll
       for (int b = 0; b < NBR; ++b) {
         if (b < nbr) {
@@ -1609,13 +1696,13 @@ __global__ __launch_bounds__(256) void branch_merge_v3_kernel(const MergeArgs a,
   const int h0 = lane / 6, h1 = (128 + lane) / 12;
   const int c0 = 8 * lane, c1 = 512 + 4 * lane;
   const bool ln = a.ln_w != nullptr;
-  const float* lw = ln ? a.ln_w : reinterpret_cast<const float*>(a.out);
-  const float* lb = ln ? a.ln_b : reinterpret_cast<const float*>(a.out);
-  float w0[8], w1[4], b0[8], b1[4];
-  load_f32<8>(lw + c0, w0);
-  load_f32<4>(lw + c1, w1);
-  load_f32<8>(lb + c0, b0);
-  load_f32<4>(lb + c1, b1);
+  float w0[8] = {}, w1[4] = {}, b0[8] = {}, b1[4] = {};
+  if (ln) {                                  // (without an LN nothing is read: the output may be a small buffer)
+    load_f32<8>(a.ln_w + c0, w0);
+    load_f32<4>(a.ln_w + c1, w1);
+    load_f32<8>(a.ln_b + c0, b0);
+    load_f32<4>(a.ln_b + c1, b1);
+  }
   // kTab: the first slide's entries, loaded once for the wave's tokens (its tokens ascend, so a crossing into
   // the next slide happens at most once)
   MergeBranch tb[kTab ? NBR : 1];
@@ -1645,7 +1732,7 @@ __global__ __launch_bounds__(256) void branch_merge_v3_kernel(const MergeArgs a,
       p = row - t_base;
     } else {
       bidx = (int)div_magic((uint32_t)row, a.dnt);
-      p = (int)a.tok_lo + (row - bidx * (int)a.ntok);
+      p = kList ? list_token(a, row - bidx * (int)a.ntok) : (int)a.tok_lo + (row - bidx * (int)a.ntok);
     }
     uint4 o0[NBR];
     uint2 o1[NBR];
@@ -1936,6 +2023,7 @@ static int attn_fwd_impl(const uint16_t* q, int64_t q_row_stride, int64_t q_tok_
   a.d_H = make_div_magic((uint32_t)H);
   a.tab = nullptr;
   a.ntab = 0;
+  a.ltab = nullptr;
   GP_REQUIRE(items < (int64_t)0x7fffffff, "gp_dilated_attn_fwd: too many work items");
   if (parts) {   // key parts (sequence-parallel under-filled launches): the 8-wave pair built with parts
     if (fmt == GP_FMT_F16_VBF16) {
@@ -2023,6 +2111,145 @@ extern "C" int gp_dilated_attn_fwd(const uint16_t* q, const uint16_t* k, const u
   }
   return gp_dilated_attn_fwd_ex(q, row_stride, 0, B, L, H, D, 0, L, br, nbranch, softmax_scale, q_log2_prescaled,
                                 fmt, stream);
+}
+
+// =========================================================================================
+// Query-list launch (ABI 12): the product attention for listed sparse rows only.  The plan (host bytes, copied
+// by the caller to device memory, as the varlen plan) holds one AttnListEntry per (batch, branch, segment, head
+// group) with a non-empty list, branches ordered by keys per item (longest first); one launch covers them all.
+namespace {
+constexpr int32_t kRowsMagic = 0x47505231;   // "GPR1"
+struct RowsHdr {
+  int32_t magic, nent, H, D;
+  int64_t L, total_items, q_stride;
+  const uint16_t* q;
+};
+constexpr int64_t kRowsTabOff = 64;
+static_assert(sizeof(RowsHdr) <= kRowsTabOff && kRowsTabOff % 16 == 0, "");
+}  // namespace
+
+extern "C" int64_t gp_attn_rows_plan_bytes(int64_t B, int64_t L, const int32_t* seg_len, const int32_t* ratios,
+                                           int nbranch) {
+  if (B < 1 || L < 1 || !seg_len || !ratios || nbranch < 1 || nbranch > GP_MAX_BRANCHES) return -1;
+  int64_t ent = 0;
+  for (int b = 0; b < nbranch; ++b) {
+    if (seg_len[b] < 1 || ratios[b] < 1) return -1;
+    const GpBranch g = gp_make_branch(L, seg_len[b], ratios[b], 1);
+    ent += (int64_t)g.nseg * g.r;
+  }
+  return kRowsTabOff + B * ent * (int64_t)sizeof(AttnListEntry);
+}
+
+extern "C" int gp_attn_rows_plan(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t row_stride,
+                                 int64_t B, int64_t L, int H, int D, const int32_t* seg_len, const int32_t* ratios,
+                                 int nbranch, const int32_t* const* grp_off, const int32_t* const* grp_rows,
+                                 uint16_t* const* o_out, float* const* lse_out, void* plan_host,
+                                 int64_t plan_bytes) {
+  GP_REQUIRE(D == 48, "gp_attn_rows_plan: head dim %d unsupported (48)", D);
+  GP_REQUIRE(q && k && v && seg_len && ratios && grp_off && grp_rows && o_out && lse_out && plan_host,
+             "gp_attn_rows_plan: null pointer");
+  GP_REQUIRE(B > 0 && L > 0 && H > 0 && row_stride >= (int64_t)H * D && row_stride % 8 == 0 && B * L < (int64_t)0x7fffffff,
+             "gp_attn_rows_plan: bad sizes");
+  GP_REQUIRE(gp_aligned(q, 16) && gp_aligned(k, 16) && gp_aligned(v, 16), "gp_attn_rows_plan: q / k / v must be 16-byte aligned");
+  const int64_t need = gp_attn_rows_plan_bytes(B, L, seg_len, ratios, nbranch);
+  GP_REQUIRE(need > 0 && plan_bytes >= need, "gp_attn_rows_plan: plan buffer of %lld bytes, %lld needed",
+             (long long)plan_bytes, (long long)need);
+  // LDS-DMA staging (attn_fwd_impl): V addressed as K + dv inside one buffer descriptor
+  const int64_t dv = (int64_t)((const char*)v - (const char*)k);
+  int order[GP_MAX_BRANCHES];
+  GpBranch geo[GP_MAX_BRANCHES];
+  for (int b = 0; b < nbranch; ++b) {
+    GP_REQUIRE(seg_len[b] > 0 && ratios[b] > 0 && grp_off[b] && grp_rows[b] && o_out[b] && lse_out[b] &&
+                   gp_aligned(o_out[b], 8), "gp_attn_rows_plan: bad branch %d", b);
+    GP_REQUIRE(dv >= 0 && 2 * row_stride >= dv + 2 * D && dv + 64 * (int64_t)ratios[b] * 2 * row_stride < 0x7fffffff,
+               "gp_attn_rows_plan: k / v must share one row layout (v at or after k)");
+    geo[b] = gp_make_branch(L, seg_len[b], ratios[b], H);
+    order[b] = b;
+  }
+  for (int x = 1; x < nbranch; ++x)
+    for (int y = x; y > 0 && geo[order[y]].m > geo[order[y - 1]].m; --y) {
+      int tmp = order[y]; order[y] = order[y - 1]; order[y - 1] = tmp;
+    }
+  const int qblk = 32 * kNWFast;
+  AttnListEntry* tab = reinterpret_cast<AttnListEntry*>(static_cast<char*>(plan_host) + kRowsTabOff);
+  int64_t items = 0, nent = 0;
+  for (int x = 0; x < nbranch; ++x) {
+    const int b = order[x];
+    const GpBranch& g = geo[b];
+    const int32_t* off = grp_off[b];
+    for (int64_t bi = 0; bi < B; ++bi)
+      for (int n = 0; n < g.nseg; ++n)
+        for (int j = 0; j < g.r; ++j) {
+          const int32_t lo = off[n * g.r + j], hi = off[n * g.r + j + 1];
+          GP_REQUIRE(lo >= 0 && hi >= lo && hi - lo <= g.m, "gp_attn_rows_plan: bad list offsets (branch %d)", b);
+          const int nheads = std::min(g.hpg, H - j * g.hpg);
+          if (hi == lo || nheads <= 0) continue;
+          AttnListEntry le;
+          memset(&le, 0, sizeof(le));
+          AttnBranch& e = le.br;
+          e.g = g;
+          e.nqb = (hi - lo + qblk - 1) / qblk;
+          e.n_lo = 0;
+          e.nseg_w = g.nseg;
+          e.kv_sparse = 0;
+          e.item_begin = items;
+          e.k = k; e.v = v;
+          e.kv_stride = row_stride;
+          e.kv_tok_base = 0;
+          e.o = o_out[b]; e.lse = lse_out[b];
+          e.kpart = 0; e.kparts = 1;
+          e.q = q; e.L = L;
+          attn_branch_magic(e);
+          le.rows = grp_rows[b] + lo;
+          le.count = hi - lo;
+          le.n = n; le.j = j; le.bidx = (int32_t)bi;
+          le.h0 = j * g.hpg;
+          tab[nent++] = le;
+          items += (int64_t)nheads * e.nqb;
+        }
+  }
+  GP_REQUIRE(items < (int64_t)0x7fffffff, "gp_attn_rows_plan: too many work items");
+  RowsHdr h;
+  memset(&h, 0, sizeof(h));
+  h.magic = kRowsMagic; h.nent = (int32_t)nent; h.H = H; h.D = D;
+  h.L = L; h.total_items = items; h.q_stride = row_stride; h.q = q;
+  memcpy(plan_host, &h, sizeof(h));
+  return 0;
+}
+
+// (4-wave blocks of 128 slots measured no faster on the 70k forward -- DESIGN §3.7 -- so one block size)
+template <bool kH>
+static void launch_attn_rows(const AttnArgs& a, hipStream_t s) {
+  constexpr int NW = kNWFast;
+  dilated_attn32_kernel<48, true, kModeFast, false, NW, kH, false, true><<<(unsigned)a.total_items, 64 * NW, 0, s>>>(a);
+  if constexpr (GP_ATTN_NOFIX == 0)
+    dilated_attn32_kernel<48, true, kModeFix, false, NW, kH, false, true><<<(unsigned)a.total_items, 64 * NW, 0, s>>>(a);
+}
+
+extern "C" int gp_dilated_attn_fwd_rows(const void* plan_host, const void* plan_dev, int q_log2_prescaled, int fmt,
+                                        void* stream) {
+  GP_REQUIRE(fmt == GP_FMT_BF16 || fmt == GP_FMT_F16_VBF16,
+             "gp_dilated_attn_fwd_rows: fmt %d unsupported (the bf16 and fp16 / bf16-V pairs)", fmt);
+  GP_REQUIRE(plan_host && plan_dev && gp_aligned(plan_dev, 16), "gp_dilated_attn_fwd_rows: null/misaligned plan");
+  const RowsHdr h = *static_cast<const RowsHdr*>(plan_host);
+  GP_REQUIRE(h.magic == kRowsMagic, "gp_dilated_attn_fwd_rows: not a gp_attn_rows_plan buffer");
+  GP_REQUIRE(h.D == 48 && q_log2_prescaled, "gp_dilated_attn_fwd_rows: needs D = 48 and a pre-scaled q");
+  if (h.total_items == 0) return 0;
+  AttnArgs a;
+  memset(&a, 0, sizeof(a));
+  a.q = h.q;
+  a.q_stride = h.q_stride;
+  a.L = h.L;
+  a.win_hi = h.L;
+  a.H = h.H;
+  a.c_log2 = 1.0f;
+  a.total_items = h.total_items;
+  a.ltab = reinterpret_cast<const AttnListEntry*>(static_cast<const char*>(plan_dev) + kRowsTabOff);
+  a.ntab = h.nent;
+  a.d_H = make_div_magic((uint32_t)h.H);
+  hipStream_t s = gp_stream(stream);
+  if (fmt == GP_FMT_F16_VBF16) launch_attn_rows<true>(a, s); else launch_attn_rows<false>(a, s);
+  return gp_check_launch("gp_dilated_attn_fwd_rows");
 }
 
 static int seg_attn(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t nbatch, int64_t seqlen, int H,
@@ -2127,6 +2354,7 @@ extern "C" int gp_branch_merge_ln_window(const uint16_t* const* o_in, const floa
   a.B = B; a.L = L; a.H = H; a.D = D; a.E = E; a.nbranch = nbranch;
   a.tok_lo = tok_lo; a.ntok = n_tok;
   a.dnt = make_div_magic((uint32_t)n_tok);
+  a.tok_list = nullptr;
   for (int b = 0; b < nbranch; ++b) {
     GP_REQUIRE(seg_len[b] > 0 && ratios[b] > 0 && o_in[b] && lse_in[b], "gp_branch_merge_ln: bad branch %d", b);
     a.br[b].g = gp_make_branch(L, seg_len[b], ratios[b], H);
@@ -2140,6 +2368,53 @@ extern "C" int gp_branch_merge_ln_window(const uint16_t* const* o_in, const floa
   if (fmt == GP_FMT_F16) launch_merge<true>(a, E, D, nbranch, nb, gp_stream(stream));
   else launch_merge<false>(a, E, D, nbranch, nb, gp_stream(stream));
   return gp_check_launch("gp_branch_merge_ln");
+}
+
+// the listed-token merge runs on branch_merge_v3_kernel alone: E = 768, D = 48, five branch entries
+extern "C" int gp_branch_merge_ln_rows_supported(int H, int D, int nbranch) {
+  return GP_MERGE_V3 != 0 && H == 16 && D == 48 && nbranch == 5;
+}
+
+extern "C" int gp_branch_merge_ln_rows(const uint16_t* const* o_in, const float* const* lse_in,
+                                       const int32_t* seg_len, const int32_t* ratios, int nbranch, int64_t B,
+                                       int64_t L, const int32_t* rows, int64_t n_rows, int H, int D,
+                                       const float* ln_w, const float* ln_b, float eps, uint16_t* out, int fmt,
+                                       void* stream) {
+  GP_REQUIRE(fmt == GP_FMT_BF16 || fmt == GP_FMT_F16, "gp_branch_merge_ln_rows: bad fmt %d", fmt);
+  GP_REQUIRE(gp_branch_merge_ln_rows_supported(H, D, nbranch),
+             "gp_branch_merge_ln_rows: H %d, D %d, %d branches unsupported (16, 48, 5)", H, D, nbranch);
+  GP_REQUIRE(B * L < (int64_t)0x7fffffff, "gp_branch_merge_ln_rows: B*L too large");
+  GP_REQUIRE(B > 0 && L > 0 && n_rows >= 0 && n_rows <= L, "gp_branch_merge_ln_rows: bad sizes");
+  if (n_rows == 0) return 0;
+  GP_REQUIRE(o_in && lse_in && seg_len && ratios && rows && out, "gp_branch_merge_ln_rows: null pointer");
+  GP_REQUIRE(ln_w == nullptr || ln_b != nullptr, "gp_branch_merge_ln_rows: ln_w without ln_b");
+  GP_REQUIRE(gp_aligned(out, 16), "gp_branch_merge_ln_rows: out must be 16-byte aligned");
+  MergeArgs a;
+  a.B = B; a.L = L; a.H = H; a.D = D; a.E = H * D; a.nbranch = nbranch;
+  a.tok_lo = 0; a.ntok = n_rows;
+  a.dnt = make_div_magic((uint32_t)n_rows);
+  a.tok_list = rows;
+  for (int b = 0; b < nbranch; ++b) {
+    GP_REQUIRE(seg_len[b] > 0 && ratios[b] > 0 && o_in[b] && lse_in[b], "gp_branch_merge_ln_rows: bad branch %d", b);
+    a.br[b].g = gp_make_branch(L, seg_len[b], ratios[b], H);
+    a.br[b].o = o_in[b];
+    a.br[b].lse = lse_in[b];
+    merge_branch_magic(a.br[b]);
+  }
+  for (int b = nbranch; b < GP_MAX_BRANCHES; ++b) a.br[b] = a.br[nbranch - 1];
+  GP_REQUIRE(merge_v2_fits(a), "gp_branch_merge_ln_rows: a branch's o rows pass 4 GiB");
+  a.ln_w = ln_w; a.ln_b = ln_b; a.eps = eps; a.out = out;
+  a.mtab = nullptr; a.tok_off = nullptr; a.nslide = 0;
+  hipStream_t s = gp_stream(stream);
+  // tokens per block as launch_merge spreads them: whole blocks per CU
+  const int64_t T = B * n_rows;
+  const int64_t ncu = attn_num_cus(s);
+  const int64_t per_cu = (T + ncu * kV3Tok - 1) / (ncu * kV3Tok);
+  const int tpb = (int)std::max<int64_t>(1, (T + ncu * per_cu - 1) / (ncu * per_cu));
+  const unsigned g = (unsigned)((T + tpb - 1) / tpb);
+  if (fmt == GP_FMT_F16) branch_merge_v3_kernel<5, true, false, true><<<g, 256, 0, s>>>(a, tpb);
+  else branch_merge_v3_kernel<5, false, false, true><<<g, 256, 0, s>>>(a, tpb);
+  return gp_check_launch("gp_branch_merge_ln_rows");
 }
 
 // =========================================================================================

@@ -42,6 +42,10 @@ struct ClsArgs {
   float eps;
   uint16_t* out;
   float* ws;
+  // compact K / V rows (gp_cls_attn_merge_ln_map): token t of a slide lies at row slide_off + row_map[t], and the
+  // slide holds map_rows rows; NULL: at row slide_off + t
+  const int32_t* row_map;
+  int32_t map_rows;
 };
 
 // sparse rows (= keys of the CLS query) of branch b at slide length L
@@ -81,7 +85,12 @@ __global__ __launch_bounds__(kChunk) void cls_attn_partial_kernel(const ClsArgs 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const bool valid = k0 + tid < m;
   const int64_t tok0 = a.slide_off[slide];
-  const int64_t tok = tok0 + (valid ? (int64_t)(k0 + tid) * a.r[b] : 0);
+  int64_t trow = valid ? (int64_t)(k0 + tid) * a.r[b] : 0;
+  if (a.row_map != nullptr) {                            // (held inside the slide's rows whatever the map says)
+    const int32_t mr = a.row_map[trow];
+    trow = mr < 0 ? 0 : (mr < a.map_rows ? mr : a.map_rows - 1);
+  }
+  const int64_t tok = tok0 + trow;
   // the key's k and v rows (D 16-bit values each, 16-byte accesses), all in flight before the first use
   const uint4* kp = reinterpret_cast<const uint4*>(a.k + tok * a.row_stride + h * D);
   const uint4* vp = reinterpret_cast<const uint4*>(a.v + tok * a.row_stride + h * D);
@@ -303,7 +312,21 @@ extern "C" int gp_cls_attn_merge_ln(const uint16_t* q, const uint16_t* k, const 
                                     int nbranch, float softmax_scale, int q_log2_prescaled, int fmt,
                                     const float* ln_w, const float* ln_b, float eps, uint16_t* out, void* ws,
                                     int64_t ws_bytes, void* stream) {
+  return gp_cls_attn_merge_ln_map(q, k, v, row_stride, slide_off, slide_len, nslide, max_len, nullptr, 0, H, D,
+                                  seg_len, ratios, nbranch, softmax_scale, q_log2_prescaled, fmt, ln_w, ln_b, eps,
+                                  out, ws, ws_bytes, stream);
+}
+
+extern "C" int gp_cls_attn_merge_ln_map(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t row_stride,
+                                        const int64_t* slide_off, const int64_t* slide_len, int64_t nslide,
+                                        int64_t max_len, const int32_t* row_map, int64_t map_rows, int H, int D,
+                                        const int32_t* seg_len, const int32_t* ratios, int nbranch,
+                                        float softmax_scale, int q_log2_prescaled, int fmt, const float* ln_w,
+                                        const float* ln_b, float eps, uint16_t* out, void* ws, int64_t ws_bytes,
+                                        void* stream) {
   gp_clear_error();
+  GP_REQUIRE(row_map == nullptr || (map_rows >= 1 && map_rows <= max_len),
+             "gp_cls_attn_merge_ln: a row map needs 1 <= map_rows (%lld) <= max_len", (long long)map_rows);
   GP_REQUIRE(fmt == GP_FMT_BF16 || fmt == GP_FMT_F16 || fmt == GP_FMT_F16_VBF16, "gp_cls_attn_merge_ln: bad fmt %d", fmt);
   GP_REQUIRE(cls_shape_ok(max_len, nslide, H, D, nbranch),
              "gp_cls_attn_merge_ln: bad shape (max_len %lld, nslide %lld, H %d, D %d in {48, 64, 96}, H*D <= 1536, "
@@ -331,6 +354,8 @@ extern "C" int gp_cls_attn_merge_ln(const uint16_t* q, const uint16_t* k, const 
   a.ln_w = ln_w; a.ln_b = ln_b; a.eps = eps;
   a.out = out;
   a.ws = static_cast<float*>(ws);
+  a.row_map = row_map;
+  a.map_rows = (int32_t)map_rows;
   hipStream_t s = gp_stream(stream);
   const dim3 grid((unsigned)items, (unsigned)nslide);
   if (D == 48) launch_partial<48>(a, fmt, grid, s);

@@ -11,11 +11,12 @@ import ctypes
 import os
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "_lib", "libgigapath_hip.so")
-ABI_VERSION = 11
+ABI_VERSION = 12
 MAX_BRANCHES = 8
 MAX_DESTS = 8
 
@@ -56,6 +57,15 @@ SIGNATURES = {
     "gp_seg_attn_fwd_f16": [c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp],
     "gp_branch_merge_ln": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_i32,
                            c_vp],
+    "gp_attn_rows_plan_bytes": [c_i64, c_i64, c_vp, c_vp, c_i32],
+    "gp_attn_rows_plan": [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
+                          c_vp, c_i64],
+    "gp_dilated_attn_fwd_rows": [c_vp, c_vp, c_i32, c_i32, c_vp],
+    "gp_branch_merge_ln_rows_supported": [c_i32, c_i32, c_i32],
+    "gp_branch_merge_ln_rows": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp,
+                                c_f32, c_vp, c_i32, c_vp],
+    "gp_cls_attn_merge_ln_map": [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i32, c_i32, c_vp,
+                                 c_vp, c_i32, c_f32, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp, c_i64, c_vp],
     "gp_cls_attn_workspace_bytes": [c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32],
     "gp_cls_attn_merge_ln": [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_f32,
                              c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp, c_i64, c_vp],
@@ -83,7 +93,7 @@ SIGNATURES = {
                             c_vp, c_f32, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i32, c_vp],
 }
 _RESTYPES = {"gp_last_error_string": ctypes.c_char_p, "gp_varlen_plan_bytes": c_i64, "gp_gemm_workspace_bytes": c_i64,
-             "gp_cls_attn_workspace_bytes": c_i64}
+             "gp_cls_attn_workspace_bytes": c_i64, "gp_attn_rows_plan_bytes": c_i64}
 
 _lib = None
 
@@ -345,6 +355,26 @@ def branch_merge_ln(outs, lses, segs, ratios, B, L, H, D, ln_w, ln_b, eps, out):
            "gp_branch_merge_ln")
 
 
+def branch_merge_ln_rows_supported(H: int, D: int, nbranch: int) -> bool:
+    """Whether branch_merge_ln_rows covers the shape (host only: works without a GPU)."""
+    return bool(load_library().gp_branch_merge_ln_rows_supported(H, D, nbranch))
+
+
+def branch_merge_ln_rows(outs, lses, segs, ratios, B, L, rows, H, D, ln_w, ln_b, eps, out):
+    """branch_merge_ln for the tokens rows[k] ([n] int32 device tensor) of every batch: out [B*n, H*D]."""
+    lib = load_library()
+    fmt = fmt_of(out.dtype)
+    _dev(out, name="out"); _dev(rows, torch.int32, "rows")
+    n = rows.numel()
+    if out.numel() != B * n * H * D:
+        raise ValueError("branch_merge_ln_rows: out must be [B * len(rows), H*D]")
+    for o in outs:
+        _dev(o, out.dtype, "o")
+    _check(lib.gp_branch_merge_ln_rows(_ptr_array(outs), _ptr_array(lses), _i32_array(segs), _i32_array(ratios),
+                                       len(segs), B, L, _ptr(rows), n, H, D, _ptr(ln_w), _ptr(ln_b), eps, _ptr(out),
+                                       fmt, _stream()), "gp_branch_merge_ln_rows")
+
+
 def cls_attn_workspace_bytes(max_len, nslide, H, D, segs, ratios) -> int:
     """Bytes of cls_attn_merge_ln's partials workspace (host only: works without a GPU)."""
     nb = int(load_library().gp_cls_attn_workspace_bytes(int(max_len), int(nslide), H, D, _i32_array(segs),
@@ -356,10 +386,12 @@ def cls_attn_workspace_bytes(max_len, nslide, H, D, segs, ratios) -> int:
 
 
 def cls_attn_merge_ln(q, k, v, row_stride, slide_off, slide_len, max_len, H, D, segs, ratios, ln_w, ln_b, eps, out,
-                      ws, softmax_scale=0.0, q_log2_prescaled=False, v_bf16=False):
+                      ws, softmax_scale=0.0, q_log2_prescaled=False, v_bf16=False, row_map=None, map_rows=0):
     """out[i] = inner_attn_ln(merge(branches)) of slide i's CLS token (gp_cls_attn_merge_ln): slide_off / slide_len
     [nslide] int64 device tensors (row of token 0, length <= max_len); out [nslide, H*D] in q's format; ws: a
-    uint8 tensor of cls_attn_workspace_bytes(...).  v_bf16: as dilated_attn_fwd."""
+    uint8 tensor of cls_attn_workspace_bytes(...).  v_bf16: as dilated_attn_fwd.  row_map ([max_len] int32 device
+    tensor) / map_rows: q / k / v hold map_rows compact rows per slide, token t at row slide_off + row_map[t]
+    (gp_cls_attn_merge_ln_map)."""
     lib = load_library()
     fmt = qkv_fmt_of(q.dtype, v_bf16)
     for t in (q, k, v):
@@ -370,10 +402,15 @@ def cls_attn_merge_ln(q, k, v, row_stride, slide_off, slide_len, max_len, H, D, 
     if slide_len.numel() != n or out.numel() != n * H * D:
         raise ValueError("cls_attn_merge_ln: slide_off, slide_len and out [nslide, H*D] disagree on nslide")
     _dev(out, q.dtype, "out"); _dev(ws, torch.uint8, "ws")
-    _check(lib.gp_cls_attn_merge_ln(_ptr(q), _ptr(k), _ptr(v), row_stride, _ptr(slide_off), _ptr(slide_len), n,
-                                    int(max_len), H, D, _i32_array(segs), _i32_array(ratios), len(segs),
-                                    float(softmax_scale), int(bool(q_log2_prescaled)), fmt, _ptr(ln_w), _ptr(ln_b),
-                                    eps, _ptr(out), _ptr(ws), ws.numel(), _stream()), "gp_cls_attn_merge_ln")
+    if row_map is not None:
+        _dev(row_map, torch.int32, "row_map")
+        if row_map.numel() < int(max_len):
+            raise ValueError("cls_attn_merge_ln: row_map must hold max_len entries")
+    _check(lib.gp_cls_attn_merge_ln_map(_ptr(q), _ptr(k), _ptr(v), row_stride, _ptr(slide_off), _ptr(slide_len), n,
+                                        int(max_len), _ptr(row_map), int(map_rows), H, D, _i32_array(segs),
+                                        _i32_array(ratios), len(segs), float(softmax_scale),
+                                        int(bool(q_log2_prescaled)), fmt, _ptr(ln_w), _ptr(ln_b), eps, _ptr(out),
+                                        _ptr(ws), ws.numel(), _stream()), "gp_cls_attn_merge_ln")
 
 
 def residual_layernorm(x, y, bias, ln_w, ln_b, eps, ln_out, rows, cols):
@@ -470,6 +507,52 @@ class VarlenPlan:
         self.dev = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(qkv.device)
         self._keep = (qkv, list(outs), list(lses))
         return self
+
+
+class AttnRowsPlan:
+    """Work table of dilated_attn_fwd_rows: the product attention for listed sparse rows of a [B, L] batch
+    (include/gigapath_hip.h "Attention for listed query rows").  groups: per branch (off, rows) int32 numpy
+    arrays -- off [nseg * r + 1], group (segment n, head group j) at n * r + j; rows the concatenated ascending
+    sparse-row lists.  The table holds device pointers into qkv / outs / lses, which must outlive its launches."""
+
+    def __init__(self, qkv: torch.Tensor, B: int, L: int, H: int, D: int, segs, ratios, groups, outs, lses):
+        lib = load_library()
+        E = H * D
+        _dev(qkv, name="qkv")
+        if qkv.dim() != 2 or qkv.shape[0] < B * L or qkv.shape[1] != 3 * E or qkv.stride(1) != 1:
+            raise ValueError("AttnRowsPlan: qkv must be [>= B*L, 3*H*D]")
+        for b, (o, l) in enumerate(zip(outs, lses)):
+            _dev(o, qkv.dtype, "o[%d]" % b); _dev(l, torch.float32, "lse[%d]" % b)
+        nb = len(segs)
+        if not (len(groups) == len(outs) == len(lses) == nb):
+            raise ValueError("AttnRowsPlan: one (off, rows) pair and one o / lse buffer per branch")
+        self.fmt = fmt_of(qkv.dtype)
+        offs = [np.ascontiguousarray(g[0], dtype=np.int32) for g in groups]
+        for b, (sl, r) in enumerate(zip(segs, ratios)):
+            s = min(int(sl), int(L))
+            if offs[b].size != -(-int(L) // s) * int(r) + 1 or int(offs[b][-1]) != np.asarray(groups[b][1]).size:
+                raise ValueError("AttnRowsPlan: branch %d offsets do not match its geometry / list" % b)
+        # (an empty list still gets a one-element device array: the table never holds a null pointer)
+        self.rows = [torch.from_numpy(np.ascontiguousarray(g[1], dtype=np.int32) if len(g[1]) else
+                                      np.zeros(1, np.int32)).to(qkv.device) for g in groups]
+        nbytes = int(lib.gp_attn_rows_plan_bytes(B, L, _i32_array(segs), _i32_array(ratios), nb))
+        if nbytes < 0:
+            raise ValueError("AttnRowsPlan: bad shape")
+        host = (ctypes.c_uint8 * nbytes)()
+        off_ptrs = (c_vp * nb)(*[o.ctypes.data for o in offs])
+        _check(lib.gp_attn_rows_plan(_ptr(qkv), _ptr(qkv[:, E:]), _ptr(qkv[:, 2 * E:]), qkv.stride(0), B, L, H, D,
+                                     _i32_array(segs), _i32_array(ratios), nb, off_ptrs, _ptr_array(self.rows),
+                                     _ptr_array(outs), _ptr_array(lses), host, nbytes), "gp_attn_rows_plan")
+        self.host = host
+        self.dev = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(qkv.device)
+        self._keep = (qkv, list(outs), list(lses), offs)
+
+
+def dilated_attn_fwd_rows(plan: AttnRowsPlan, q_log2_prescaled: bool = True, v_bf16: bool = False):
+    lib = load_library()
+    fmt = FMT_F16_VBF16 if (v_bf16 and plan.fmt == FMT_F16) else plan.fmt
+    _check(lib.gp_dilated_attn_fwd_rows(plan.host, _ptr(plan.dev), int(bool(q_log2_prescaled)), fmt, _stream()),
+           "gp_dilated_attn_fwd_rows")
 
 
 def dilated_attn_fwd_varlen(plan: VarlenPlan, q_log2_prescaled: bool = True, v_bf16: bool = False):

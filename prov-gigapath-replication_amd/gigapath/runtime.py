@@ -29,7 +29,9 @@ across calls of the same shape.  No CPU fallback exists: every non-GEMM op is a 
 
 When the caller reads only the CLS row of each slide (LongNetViT with global_pool off), the last layer runs its
 QKV GEMM in full and the rest for those rows alone (cls_tail: gp_cls_attn_merge_ln, then the same entry points
-at M = slides).
+at M = slides).  On the dense [B, L] forward the layer before it then runs, after its attention, for
+the rows the CLS query's keys name (key_row_tail: gp_branch_merge_ln_rows, the same entry points at M = B |S|, the
+last QKV GEMM on those rows and gp_cls_attn_merge_ln_map).
 """
 from __future__ import annotations
 
@@ -597,8 +599,89 @@ class ClsRows:
                                    dtype=torch.uint8, device=dev)
 
 
+def key_row_plan(L: int, segs: Sequence[int], ratios: Sequence[int]):
+    """The tokens whose K / V the CLS query of a slide of L tokens reads: branch (sl, r) with
+    s = min(sl, L), m = ceil(s / r) attends tokens 0, r, ..., (m - 1) r.  Returns (rows, row_map, groups):
+      rows     sorted int32 array S, the union over the branches;
+      row_map  int32 [L]: row_map[S[k]] = k, -1 for a token outside S;
+      groups   per branch (off, idx): the sparse rows the merge reads for the tokens of S.  Token p comes from
+               sparse row i of (segment n, head group j) with p = n g + i r + j, g = m r (sparse_to_dense,
+               dilated_attention.py:33-53; g = s, so p is that row's own query token, wherever r divides s or the
+               branch has one segment); idx[off[n r + j] : off[n r + j + 1]] lists the i of that group, ascending."""
+    L = int(L)
+    mark = np.zeros(L, dtype=bool)
+    for sl, r in zip(segs, ratios):
+        s, _, m = branch_geometry(L, sl, r)
+        mark[np.arange(m, dtype=np.int64) * r] = True
+    rows = np.flatnonzero(mark).astype(np.int32)
+    row_map = np.full(L, -1, dtype=np.int32)
+    row_map[rows] = np.arange(rows.size, dtype=np.int32)
+    groups = []
+    t = rows.astype(np.int64)
+    for sl, r in zip(segs, ratios):
+        s, nseg, m = branch_geometry(L, sl, r)
+        n, w = t // (m * r), t % (m * r)
+        g = n * r + w % r
+        order = np.argsort(g, kind="stable")           # (tokens ascend within a group, so i does)
+        off = np.zeros(nseg * r + 1, dtype=np.int32)
+        np.cumsum(np.bincount(g, minlength=nseg * r), out=off[1:])
+        groups.append((off, (w // r)[order].astype(np.int32)))
+    return rows, row_map, groups
+
+
+class KeyRows:
+    """Buffers of the key-row tail (EncoderEngine.key_row_tail): the second-to-last layer after its attention, and
+    the last layer's QKV GEMM, on the n = |S| rows per slide that the CLS tail reads (key_row_plan).  One list for
+    every slide of the [B, L] batch; slide b's rows are compact rows [b n, (b + 1) n), its CLS first.  Everything
+    here is fixed by the workspace key and lives as long as the workspace: a HIP graph bakes the pointers."""
+
+    def __init__(self, dev, B: int, L: int, E: int, F: int, plan, act: torch.dtype):
+        rows, row_map, self.groups = plan
+        self._attn_plan = None
+        n = int(rows.size)
+        self.n, self.M = n, B * n
+        self.rows = torch.from_numpy(rows).to(dev)                       # [n] int32: the tokens S
+        self.row_map = torch.from_numpy(row_map).to(dev)                 # [L] int32: token -> compact row
+        gather = (np.arange(B, dtype=np.int64)[:, None] * L + rows.astype(np.int64)[None, :]).reshape(-1)
+        self.gather = torch.from_numpy(gather).to(dev)                   # [B n] int64: rows of ws.x
+        self.off = torch.arange(B, dtype=torch.int64, device=dev) * n    # each slide's first compact row (its CLS)
+        M = self.M
+        self.x = torch.empty(M, E, dtype=torch.float32, device=dev)
+        self.a = torch.empty(M, E, dtype=act, device=dev)
+        self.y = torch.empty(M, E, dtype=act, device=dev)
+        self.y2 = torch.empty(M, E, dtype=act, device=dev)
+        self.f = torch.empty(M, F, dtype=act, device=dev)
+        self.qkv = torch.empty(M, 3 * E, dtype=act, device=dev)          # the last layer's (V third: see Workspace)
+        self.fstats, self.gemm_ws = ffn_buffers(dev, M, E, F)
+
+    def attn_rows_plan(self, ws, pa: "PackedAttention", B: int, L: int):
+        """The query-list attention's work table bound to ws.qkv and ws.attn (built once), or None where the
+        list launch does not cover the call: a q that is not pre-scaled, or fp16 with an fp16 V (the exact
+        running-max kernel has no list variant); the full launch then runs."""
+        if not pa.prescaled or pa.D != 48 or (ws.qkv.dtype == torch.float16 and not pa.v_bf16):
+            return None
+        if self._attn_plan is None:
+            self._attn_plan = _hip.AttnRowsPlan(ws.qkv, B, L, pa.H, pa.D, pa.segs, pa.ratios, self.groups,
+                                                ws.attn.outs, ws.attn.lses)
+        return self._attn_plan
+
+
 class Workspace:
     cls: Optional[ClsRows] = None
+    _key_rows = None        # unset; False: the key-row tail does not apply at this shape
+
+    def key_rows(self) -> Optional[KeyRows]:
+        """The key-row tail's buffers (built on first use), or None where it does not engage: more than
+        KEYROW_MAX_SHARE of the rows are needed, or gp_branch_merge_ln_rows does not cover the shape."""
+        if self._key_rows is None:
+            self._key_rows = False
+            B, L, E, F, H = self.key[1:6]
+            segs, ratios, act = self.key[-3], self.key[-2], self.key[-1]
+            if _hip.branch_merge_ln_rows_supported(H, E // H, len(segs)):
+                plan = key_row_plan(L, segs, ratios)
+                if plan[0].size <= KEYROW_MAX_SHARE * L:
+                    self._key_rows = KeyRows(self.x.device, B, L, E, F, plan, act)
+        return self._key_rows or None
 
     def cls_rows(self) -> ClsRows:
         """The CLS tail's buffers, allocated on first use (an eager run precedes every graph capture)."""
@@ -654,6 +737,9 @@ class PackedWorkspace(Workspace):
 
     def _slides(self):
         return self.tok_off[:-1], self.Ls
+
+    def key_rows(self):
+        return None          # (the packed forward keeps the full second-to-last layer)
 
 
 class EncoderEngine:
@@ -740,6 +826,20 @@ class EncoderEngine:
         if self.pws is ws:
             self.pws = None
 
+    def _resid_fused_path(self, ws) -> bool:
+        return bool(self.layers) and all(pl.resid_fused for pl in self.layers) and ws.fstats is not None
+
+    def key_row_tail(self, ws, cls_rows: Optional[ClsRows]) -> Optional[KeyRows]:
+        """The KeyRows run_layers(ws, ..., cls_rows=cls_rows) runs the second-to-last layer on, or None: that
+        layer's output feeds only the last layer's K / V rows of the CLS query's keys and the CLS readout, so
+        with the CLS tail on it runs for those rows alone.  Not on the packed forward, the
+        residual-epilogue path, models of fewer than 3 layers, or where Workspace.key_rows() declines.  When
+        taken, ws.x keeps the output of layer depth-3 and layer depth-2's output is KeyRows.x (slide b's CLS at
+        row KeyRows.off[b])."""
+        if cls_rows is None or not KEYROW_TAIL or len(self.layers) < 3 or self._resid_fused_path(ws):
+            return None
+        return ws.key_rows()
+
     def run_layers(self, ws: Workspace, B: int, L: int, layer_hook=None, shift_ready: bool = False,
                    cls_rows: Optional[ClsRows] = None):
         """ws.x holds the fp32 embedding and ws.a = LN1_0(ws.x) (16-bit).  Runs every layer in
@@ -752,7 +852,7 @@ class EncoderEngine:
         E = ws.x.shape[1]
         F = ws.f.shape[1]
         nl = len(self.layers)
-        if self.layers and all(pl.resid_fused for pl in self.layers) and ws.fstats is not None:
+        if self._resid_fused_path(ws):
             if not shift_ready:
                 torch.mean(ws.x, 1, out=ws.shift[0])
             for li, pl in enumerate(self.layers):
@@ -770,12 +870,24 @@ class EncoderEngine:
                 if layer_hook is not None:
                     layer_hook(li + 1)
             return
+        kr = self.key_row_tail(ws, cls_rows)
         for li, pl in enumerate(self.layers):
             pa = pl.attn
+            if cls_rows is not None and li + 1 == nl:
+                if kr is not None:
+                    with TIMER.span("keyrow_tail"):
+                        linear(kr.a, pa.w_qkv, pa.b_qkv, pa.b_qkv_f32, kr.qkv, kr.gemm_ws, v_bf16=pa.v_bf16)
+                else:
+                    with TIMER.span("gemm_qkv"):
+                        linear(ws.a, pa.w_qkv, pa.b_qkv, pa.b_qkv_f32, ws.qkv, ws.gemm_ws, v_bf16=pa.v_bf16)
+                cls_tail(pl, ws, cls_rows, kr)
+                if layer_hook is not None:
+                    layer_hook(li + 1)
+                continue
             with TIMER.span("gemm_qkv"):
                 linear(ws.a, pa.w_qkv, pa.b_qkv, pa.b_qkv_f32, ws.qkv, ws.gemm_ws, v_bf16=pa.v_bf16)
-            if cls_rows is not None and li + 1 == nl:
-                cls_tail(pl, ws, cls_rows)
+            if kr is not None and li + 2 == nl:
+                key_row_layer(pl, self.layers[li + 1], ws, kr, B, L)
                 if layer_hook is not None:
                     layer_hook(li + 1)
                 continue
@@ -818,20 +930,58 @@ def residual_pair(pl: "PackedLayer", nxt: Optional["PackedLayer"], ws, M: int, E
 CLS_TAIL = os.environ.get("GIGAPATH_CLS_TAIL", "1") != "0"
 
 
-def cls_tail(pl: "PackedLayer", ws, c: ClsRows):
+# the second-to-last layer for the rows the CLS tail reads (key_row_layer).  =0 restores the full layer; means
+# nothing unless the CLS tail is on.
+KEYROW_TAIL = os.environ.get("GIGAPATH_KEYROW_TAIL", "1") != "0"
+# engaged where at most this share of a slide's rows is needed (|S| <= L / 2: L >= 7,842 on the product schedule;
+# below it tests/test_gpu_cls_tail.py's on / off bit-identity of the earlier layers holds by not engaging)
+KEYROW_MAX_SHARE = 0.5
+
+
+def key_row_layer(pl: "PackedLayer", nxt: "PackedLayer", ws, kr: KeyRows, B: int, L: int):
+    """Encoder layer depth-2 after its QKV GEMM wrote ws.qkv, for the rows kr.rows of every slide: the attention
+    of the sparse rows their merge reads (gp_dilated_attn_fwd_rows; every key is still attended to), then the
+    branch merge + inner LN of the listed tokens into the compact kr.a and EncoderLayer.forward's remaining steps (encoder.py:141-162) at M = B |S| on
+    kr's buffers, as residual_pair runs them.  Leaves kr.x (the layer's output rows) and kr.a = the last layer's
+    LN1 of them; ws.x keeps the layer's input."""
+    pa = pl.attn
+    E, F, M = pa.E, kr.f.shape[1], kr.M
+    plan = kr.attn_rows_plan(ws, pa, B, L)
+    if plan is not None:
+        with TIMER.span("keyrow_attn"):
+            _hip.dilated_attn_fwd_rows(plan, True, v_bf16=pa.v_bf16)
+    else:
+        with TIMER.span("attn"):
+            _hip.dilated_attn_fwd(ws.qkv, ws.qkv[:, E:], ws.qkv[:, 2 * E:], 3 * E, B, L, pa.H, pa.D, pa.segs,
+                                  pa.ratios, ws.attn.outs, ws.attn.lses, 0.0, pa.prescaled, v_bf16=pa.v_bf16)
+    with TIMER.span("keyrow_merge"):
+        _hip.branch_merge_ln_rows(ws.attn.outs, ws.attn.lses, pa.segs, pa.ratios, B, L, kr.rows, pa.H, pa.D,
+                                  pa.ln_w, pa.ln_b, pa.ln_eps, kr.a)
+    with TIMER.span("keyrow_tail"):
+        torch.index_select(ws.x, 0, kr.gather, out=kr.x)
+        linear(kr.a, pa.w_o, None, None, kr.y, kr.gemm_ws)
+        _hip.residual2_layernorm(kr.x, kr.y, pa.b_o, None, None, pl.ln2_w, pl.ln2_b, pl.ln2_eps, kr.a, M, E)
+        b2 = ffn_forward(pl, kr.a, kr.f, kr.y2, kr.fstats, kr.gemm_ws, M, F, timed=False)
+        _hip.residual2_layernorm(kr.x, kr.y, pa.b_o, kr.y2, b2, nxt.ln1_w, nxt.ln1_b, nxt.ln1_eps, kr.a, M, E)
+
+
+def cls_tail(pl: "PackedLayer", ws, c: ClsRows, kr: Optional[KeyRows] = None):
     """The last encoder layer after its QKV GEMM wrote ws.qkv, for the CLS token of every slide: the row the
     readout outcome = self.norm(x)[:, 0] (slide_encoder.py:213-221) takes from that layer.  The CLS query's
     attention, branch merge and inner LN in gp_cls_attn_merge_ln (K / V of every token it attends to come from
     ws.qkv), then EncoderLayer.forward's remaining steps (encoder.py:141-162) at M = n rows on c's buffers:
-    out-proj, residual + LN2, FFN, residual.  Result: c.x [n, E] fp32."""
+    out-proj, residual + LN2, FFN, residual.  Result: c.x [n, E] fp32.  kr (the key-row tail): the layer's qkv and
+    input rows are the compact kr.qkv / kr.x, token t of slide b at row kr.off[b] + kr.row_map[t]."""
     pa = pl.attn
     n, E, F = c.n, pa.E, c.f.shape[1]
-    q, k, v = ws.qkv, ws.qkv[:, E:], ws.qkv[:, 2 * E:]
+    qkv, x, off = (ws.qkv, ws.x, c.off) if kr is None else (kr.qkv, kr.x, kr.off)
+    q, k, v = qkv, qkv[:, E:], qkv[:, 2 * E:]
     with TIMER.span("cls_attn"):
-        _hip.cls_attn_merge_ln(q, k, v, 3 * E, c.off, c.len, c.max_len, pa.H, pa.D, pa.segs, pa.ratios, pa.ln_w,
-                               pa.ln_b, pa.ln_eps, c.a, c.attn_ws, 0.0, pa.prescaled, v_bf16=pa.v_bf16)
+        _hip.cls_attn_merge_ln(q, k, v, 3 * E, off, c.len, c.max_len, pa.H, pa.D, pa.segs, pa.ratios, pa.ln_w,
+                               pa.ln_b, pa.ln_eps, c.a, c.attn_ws, 0.0, pa.prescaled, v_bf16=pa.v_bf16,
+                               row_map=None if kr is None else kr.row_map, map_rows=0 if kr is None else kr.n)
     with TIMER.span("cls_tail"):
-        torch.index_select(ws.x, 0, c.off, out=c.x)
+        torch.index_select(x, 0, off, out=c.x)
         linear(c.a, pa.w_o, None, None, c.y, c.gemm_ws)
         _hip.residual2_layernorm(c.x, c.y, pa.b_o, None, None, pl.ln2_w, pl.ln2_b, pl.ln2_eps, c.a, n, E)
         b2 = ffn_forward(pl, c.a, c.f, c.y2, c.fstats, c.gemm_ws, n, F, timed=False)

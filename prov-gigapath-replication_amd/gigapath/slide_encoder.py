@@ -276,7 +276,7 @@ class LongNetViT(nn.Module):
         self.encoder.engine.pack(self.encoder, dev)
         key = (str(dev), int(torch.cuda.current_stream(dev).cuda_stream), tuple(x.shape), x.dtype, c.dtype,
                runtime.act_dtype(), bool(all_layer_embed), bool(self.global_pool), bool(runtime.CLS_TAIL),
-               self._top_sig, self.encoder.engine._sig)
+               bool(runtime.KEYROW_TAIL), self._top_sig, self.encoder.engine._sig)
         ent = self._graph_lookup(key)
         if ent is None and self._graph_wanted(key):
             ent = self._capture(key, x, c, lambda sx, sc: self._forward_device(sx, sc, all_layer_embed, False),
@@ -542,6 +542,9 @@ class LongNetViT(nn.Module):
         # only the CLS rows are read (outcome = self.norm(x)[:, 0], reference :221): the last layer runs for
         # them alone (runtime.cls_tail) and leaves them in cls.x [B, E]; global_pool reads every row
         cls = ws.cls_rows() if (runtime.CLS_TAIL and not self.global_pool) else None
+        # ... and the layer before it for the rows the tail reads (runtime.key_row_layer): its CLS rows are the
+        # first compact row of each slide in kr.x
+        kr = eng.key_row_tail(ws, cls)
 
         def readout(slot: int):
             if self.global_pool:
@@ -549,6 +552,8 @@ class LongNetViT(nn.Module):
                 _hip.layernorm_f32(pool, E, top["norm_w"], top["norm_b"], top["norm_eps"], res[slot], B, E)
             elif cls is not None and slot == len(layers):
                 _hip.layernorm_f32(cls.x, E, top["norm_w"], top["norm_b"], top["norm_eps"], res[slot], B, E)
+            elif kr is not None and slot == len(layers) - 1:
+                _hip.layernorm_f32(kr.x, kr.n * E, top["norm_w"], top["norm_b"], top["norm_eps"], res[slot], B, E)
             else:
                 _hip.layernorm_f32(ws.x, L * E, top["norm_w"], top["norm_b"], top["norm_eps"], res[slot], B, E)
 
