@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GP_ABI_VERSION 12
+#define GP_ABI_VERSION 13
 #define GP_EARG (-1)
 #define GP_MAX_BRANCHES 8
 #define GP_MAX_DESTS 8
@@ -192,6 +192,28 @@ int gp_seg_attn_fwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, int
 int gp_seg_attn_fwd_f16(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t nbatch,
                         int64_t seqlen, int H, int D, float softmax_scale, uint16_t* o, float* lse,
                         void* stream);
+
+/* ---- Backward of the seam (ABI 13): (dq, dk, dv) of gp_seg_attn_fwd[_f16]'s attention.
+ * Bytes of gp_seg_attn_bwd's workspace (the fp32 delta_i = sum_d dout_id o_id, [nbatch, H, seqlen], rounded up
+ * to 256); 0 on a bad shape.  Host only.  Part of what replaces flash-attn's backward behind flash_attn_func
+ * (torchscale/component/flash_attention.py:13-16). */
+size_t gp_seg_attn_bwd_workspace_bytes(int64_t nbatch, int64_t seqlen, int H, int D);
+
+/* Replaces flash-attn's backward behind flash_attn_func (torchscale/component/flash_attention.py:13-16):
+ * non-causal, no mask, dropout 0.  The LSE takes no gradient: DilatedAttention.scattering computes the branch
+ * weights from it under torch.no_grad() (dilated_attention.py:119-124), and flash-attn's own autograd function
+ * ignores it.  q / k / v / o / dout and dq / dk / dv: [nbatch, seqlen, H, D] contiguous, 16-byte aligned, in fmt
+ * (GP_FMT_BF16 or GP_FMT_F16); lse: [nbatch, H, seqlen] fp32 as gp_seg_attn_fwd[_f16] wrote it; o: that call's
+ * output.  D in {48, 64, 96}; softmax_scale 0 = D^-1/2.  P = exp(c q.k - lse) is recomputed; dv = P^T dout,
+ * dS = P o (dout v^T - delta), dq = c dS k, dk = c dS^T q; fp32 accumulation, P and dS rounded to fmt as MFMA
+ * operands, results rounded once.  Two launches (a workgroup owns 128 query rows, then 128 keys), no atomics:
+ * results are bitwise reproducible.  Non-finite dout yields non-finite gradients (GradScaler relies on it).
+ * workspace: gp_seg_attn_bwd_workspace_bytes(...) bytes, 16-byte aligned.  Every argument error is rejected
+ * before any launch. */
+int gp_seg_attn_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* o,
+                    const float* lse, const uint16_t* dout, int64_t nbatch, int64_t seqlen, int H, int D,
+                    float softmax_scale, uint16_t* dq, uint16_t* dk, uint16_t* dv,
+                    void* workspace, size_t workspace_bytes, int fmt, void* stream);
 
 /* Branch merge (DilatedAttention.scattering / sparse_to_dense, dilated_attention.py:33-53,
  * 100-131) fused with inner_attn_ln (:212-213):

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from collections import OrderedDict
 from typing import Optional, Sequence
 
 import numpy as np
@@ -16,7 +17,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "_lib", "libgigapath_hip.so")
-ABI_VERSION = 12
+ABI_VERSION = 13
 MAX_BRANCHES = 8
 MAX_DESTS = 8
 
@@ -55,6 +56,9 @@ SIGNATURES = {
                                   c_f32, c_vp, c_i32, c_vp],
     "gp_seg_attn_fwd": [c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp],
     "gp_seg_attn_fwd_f16": [c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp],
+    "gp_seg_attn_bwd_workspace_bytes": [c_i64, c_i64, c_i32, c_i32],
+    "gp_seg_attn_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp,
+                        ctypes.c_size_t, c_i32, c_vp],
     "gp_branch_merge_ln": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_i32,
                            c_vp],
     "gp_attn_rows_plan_bytes": [c_i64, c_i64, c_vp, c_vp, c_i32],
@@ -93,7 +97,8 @@ SIGNATURES = {
                             c_vp, c_f32, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i32, c_vp],
 }
 _RESTYPES = {"gp_last_error_string": ctypes.c_char_p, "gp_varlen_plan_bytes": c_i64, "gp_gemm_workspace_bytes": c_i64,
-             "gp_cls_attn_workspace_bytes": c_i64, "gp_attn_rows_plan_bytes": c_i64}
+             "gp_cls_attn_workspace_bytes": c_i64, "gp_attn_rows_plan_bytes": c_i64,
+             "gp_seg_attn_bwd_workspace_bytes": ctypes.c_size_t}
 
 _lib = None
 
@@ -342,6 +347,43 @@ def seg_attn_fwd(q, k, v, o, lse, softmax_scale=0.0):
     fn, name = (lib.gp_seg_attn_fwd_f16, "gp_seg_attn_fwd_f16") if dt == torch.float16 else \
         (lib.gp_seg_attn_fwd, "gp_seg_attn_fwd")
     _check(fn(_ptr(q), _ptr(k), _ptr(v), nb, sl, H, D, float(softmax_scale), _ptr(o), _ptr(lse), _stream()), name)
+
+
+# gp_seg_attn_bwd's workspace (the fp32 delta): one grow-only buffer per (device, stream), so two streams never
+# share it; bounded, oldest first, for callers that use a fresh stream per request
+_BWD_WS: "OrderedDict[tuple, torch.Tensor]" = OrderedDict()
+_BWD_WS_MAX = 8
+
+
+def _bwd_workspace(dev: torch.device, nbytes: int) -> torch.Tensor:
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), _stream())
+    ws = _BWD_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        while key not in _BWD_WS and len(_BWD_WS) >= _BWD_WS_MAX:
+            _BWD_WS.popitem(last=False)
+        ws = _BWD_WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _BWD_WS.move_to_end(key)
+    return ws
+
+
+def seg_attn_bwd(q, k, v, o, lse, dout, dq, dk, dv, softmax_scale=0.0):
+    """Backward of the flash_attn_func seam (gp_seg_attn_bwd): q / k / v / o / dout and dq / dk / dv
+    [nbatch, seqlen, H, D] in one 16-bit dtype, lse [nbatch, H, seqlen] fp32 as seg_attn_fwd wrote it."""
+    lib = load_library()
+    nb, sl, H, D = q.shape
+    fmt = fmt_of(q.dtype)
+    for nm, t in (("q", q), ("k", k), ("v", v), ("o", o), ("dout", dout), ("dq", dq), ("dk", dk), ("dv", dv)):
+        _dev(t, q.dtype, nm)
+        if t.shape != q.shape:
+            raise ValueError("seg_attn_bwd: %s is %s, q is %s" % (nm, tuple(t.shape), tuple(q.shape)))
+    _dev(lse, torch.float32, "lse")
+    if lse.shape != (nb, H, sl):
+        raise ValueError("seg_attn_bwd: lse is %s, expected %s" % (tuple(lse.shape), (nb, H, sl)))
+    need = int(lib.gp_seg_attn_bwd_workspace_bytes(nb, sl, H, D))
+    ws = _bwd_workspace(q.device, max(need, 256))
+    _check(lib.gp_seg_attn_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), _ptr(dout), nb, sl, H, D,
+                               float(softmax_scale), _ptr(dq), _ptr(dk), _ptr(dv), ws.data_ptr(), ws.numel(), fmt,
+                               _stream()), "gp_seg_attn_bwd")
 
 
 def branch_merge_ln(outs, lses, segs, ratios, B, L, H, D, ln_w, ln_b, eps, out):
