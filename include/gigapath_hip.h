@@ -215,6 +215,50 @@ int gp_seg_attn_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, con
                     float softmax_scale, uint16_t* dq, uint16_t* dk, uint16_t* dv,
                     void* workspace, size_t workspace_bytes, int fmt, void* stream);
 
+/* ---- Backward of the fused dilated attention (added under ABI 13; purely additive, the version stays 13):
+ * (dq, dk, dv) of the composite merged = gp_branch_merge_ln(gp_dilated_attn_fwd(q, k, v)) with ln_w == NULL,
+ * given dmerged = d loss / d merged.  Replaces autograd's backward of DilatedAttention.forward between the
+ * projections and inner_attn_ln (dilated_attention.py:133-211): per branch the backward of gathering x3
+ * (:76-98, index_add), of flash_attn_func (torchscale/component/flash_attention.py:13-16) and of scattering
+ * (:100-131).
+ *
+ * gp_dilated_attn_bwd_workspace_bytes: bytes of the workspace (per branch the 16-bit dout_b and the fp32 delta_b
+ * in the branch's own [B*nseg, m, H, D] / [B*nseg, H, m] layouts, then three fp32 [B*L, H*D] accumulators, each
+ * rounded up to 256); 0 on a bad shape.  Host only.
+ *
+ * gp_dilated_attn_bwd: q / k / v / row_stride / B / L / H / D / seg_len / ratios / nbranch / softmax_scale /
+ * q_log2_prescaled as the forward call's (row_stride >= H*D, a multiple of 8); o_in / lse_in: HOST tables of that
+ * call's nbranch output pointers; dmerged: [B*L, H*D] in fmt, contiguous.  dq / dk / dv: rows of d_row_stride
+ * elements (>= H*D, a multiple of 8; a fused [B*L, 3E] dqkv passes base, base + E, base + 2E and 3E).  fmt:
+ * GP_FMT_BF16 or GP_FMT_F16 (GP_FMT_F16_VBF16 is rejected).  D in {48, 64, 96}; q_log2_prescaled only with
+ * D in {48, 64}: the gradient is then taken with respect to the pre-scaled q' the forward received (logits
+ * q'.k ln 2: dq' = ln 2 dS k, dk = ln 2 dS^T q').
+ *   - The branch weights take no gradient (dilated_attention.py:119-124, torch.no_grad()): sparse row (n, i, h)
+ *     of branch b, phase j = h / (Hp/r), receives dout_b = w_b * dmerged[slot n*g + i*r + j] (g = m*r; zero if the
+ *     slot >= L), w_b the merge's weight (uncovered or lse == 0 -> -1e8, fp32 softmax over the branches).
+ *   - The row reads q / k / v at token n*s + i*r + j, a zero pad where i*r + j >= s or the token >= L, as the
+ *     forward does.  Where s % r != 0 the merge reads rows of zero-padded queries: their dq and their dk
+ *     contribution are 0, their dv contribution is not.  Zero-pad keys are in the LSE and contribute nothing else.
+ *   - P = exp(logit - lse) is recomputed from the saved LSE (as gp_seg_attn_bwd: dv = P^T dout, dS = P o (dout v^T
+ *     - delta), P and dS rounded to fmt as MFMA operands; for dq, delta is corrected to first order from the
+ *     recomputed P and dS enters as the rounded value plus its rounded remainder, so dq is the fp32 result rounded
+ *     once).  Rows the forward leaves unwritten are never read.
+ *   - Every element of dq / dk / dv for tokens [0, L) of each batch and all H*D columns is written (0 where no
+ *     branch covers the (token, head)); nothing else is.  fp32 accumulation within and across branches in
+ *     branch order, one rounding to fmt on store.  No atomics: two calls give the same bits.
+ *   - A non-finite dmerged yields non-finite gradients (GradScaler relies on it).
+ * workspace: gp_dilated_attn_bwd_workspace_bytes(...) bytes, 16-byte aligned.  All pointers 16-byte aligned
+ * (lse_in entries 4).  Every argument error is rejected before any launch.  Launches: a memset of the
+ * accumulators, the merge backward, two attention kernels per branch, the store. */
+size_t gp_dilated_attn_bwd_workspace_bytes(int64_t B, int64_t L, int H, int D, const int32_t* seg_len,
+                                           const int32_t* ratios, int nbranch);
+int gp_dilated_attn_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t row_stride,
+                        int64_t B, int64_t L, int H, int D, const int32_t* seg_len, const int32_t* ratios,
+                        int nbranch, const uint16_t* const* o_in, const float* const* lse_in,
+                        const uint16_t* dmerged, float softmax_scale, int q_log2_prescaled,
+                        uint16_t* dq, uint16_t* dk, uint16_t* dv, int64_t d_row_stride,
+                        void* workspace, size_t workspace_bytes, int fmt, void* stream);
+
 /* Branch merge (DilatedAttention.scattering / sparse_to_dense, dilated_attention.py:33-53,
  * 100-131) fused with inner_attn_ln (:212-213):
  *   per (token p, head h): lse_b = covered ? lse_b[..] : -1e8, lse_b == 0 -> -1e8,

@@ -19,7 +19,21 @@
 // on store.  Tails by predication: rows past seqlen are loaded as zeros and never stored, a tail key gets
 // P = 0 by a select, a tail query gets lse = +inf.  This file is compiled with NaNs honoured: a non-finite
 // dout reaches all three gradients.
+//
+// The same two kernels, templated over the addressing (kDil), are the backward of the fused dilated attention
+// (gp_dilated_attn_bwd: gp_dilated_attn_fwd + the no-LN gp_branch_merge_ln; DilatedAttention.forward,
+// dilated_attention.py:133-211).  There a work item is (segment, head, 128-row tile) of one branch and the dilated
+// gather is folded into the addressing, as in the forward: sparse row i of segment n and head h (phase
+// j = h / hpg) reads q / k / v at token n s + i r + j (row stride r * row_stride; a zero pad where i r + j >= s or
+// the token >= L) and its dout / lse / delta at row i of the branch's own [B nseg, m, H, D] / [B nseg, H, m]
+// buffers.  Three row counts replace seqlen: nk valid keys (= rows with a real q), nq rows that carry a dout
+// (merge slot n g + i r + j < L: exactly the rows the forward wrote), min(nk, nq) rows whose dq is stored.
+// merge_bwd_kernel writes dout_b = w_b dmerged first; the branches then run in order and add into
+// fp32 accumulators (a (token, head) belongs to one sparse row per branch: plain read-add-write, no atomics),
+// which grad_store_kernel rounds once.
 #include <math.h>
+
+#include <type_traits>
 
 #include "gp_api.h"
 #include "gp_common.h"
@@ -65,6 +79,78 @@ struct BwdArgs {
   int32_t ntile;         // ceil(L / kOwn)
   float c, c_log2;       // softmax_scale, softmax_scale * log2(e)
 };
+
+// One branch of gp_dilated_attn_bwd (kDil): dense q / k / v rows, the branch's own dout / lse / delta buffers.
+struct DilArgs {
+  const uint16_t *q, *k, *v;     // [B*L, row_stride], head h at columns h*D
+  const uint16_t *o, *dout;      // [B*nseg, m, H, D]: the forward's o_b; w_b * dmerged (merge_bwd_kernel)
+  const float* lse;              // [B*nseg, H, m]
+  float* delta;                  // [B*nseg, H, m] fp32 (workspace)
+  float *gq, *gk, *gv;           // fp32 accumulators [B*L, H*D]
+  int64_t row_stride, L;
+  GpBranch g;
+  int32_t H;
+  int32_t ntile;                 // ceil(m / kOwn)
+  float c, c_log2;               // factor of dq / dk; factor of q.k in the log2-domain logit
+};
+
+// What one work item (a (batch, head) of the seam, a (segment, head) of a dilated branch) addresses.
+struct View {
+  const uint16_t *q, *k, *v, *dout, *o;
+  const float* lse;
+  float* delta;
+  uint16_t *dq, *dk, *dv;        // seam: 16-bit results, row stride rs
+  float *gq, *gk, *gv;           // dilated: fp32 accumulators, row stride grs
+  int64_t rs, rso, grs;          // row strides of q / k / v, of o / dout, of the accumulators
+  int nk, nq;                    // valid keys (= rows with a real q); query rows that carry a dout
+  int npad;                      // zero-pad keys in the saved LSE (score 0, v = 0): m - nk; the seam has none
+};
+
+template <int D>
+GP_DEV void make_view(const BwdArgs& a, int64_t bh, View& w) {
+  const int b = (int)(bh / a.H), h = (int)(bh % a.H);
+  const int64_t base = ((int64_t)b * a.L * a.H + h) * D;
+  w.q = a.q + base; w.k = a.k + base; w.v = a.v + base; w.dout = a.dout + base; w.o = a.o + base;
+  w.lse = a.lse + bh * a.L;
+  w.delta = a.delta + bh * a.L;
+  w.dq = a.dq + base; w.dk = a.dk + base; w.dv = a.dv + base;
+  w.gq = w.gk = w.gv = nullptr;
+  w.rs = w.rso = (int64_t)a.H * D;
+  w.grs = 0;
+  w.nk = w.nq = a.L;
+  w.npad = 0;
+}
+template <int D>
+GP_DEV void make_view(const DilArgs& a, int64_t bh, View& w) {
+  const GpBranch& g = a.g;
+  const int bn = (int)(bh / a.H), h = (int)(bh % a.H);
+  const int bidx = bn / g.nseg, n = bn % g.nseg, j = h / g.hpg;
+  const int64_t tok0 = (int64_t)bidx * a.L + (int64_t)n * g.s + j;      // the token of sparse row 0
+  const int64_t off = tok0 * a.row_stride + h * D;
+  w.q = a.q + off; w.k = a.k + off; w.v = a.v + off;
+  const int64_t ooff = ((int64_t)bn * g.m * a.H + h) * D;
+  w.dout = a.dout + ooff;
+  w.o = a.o + ooff;
+  const int64_t soff = ((int64_t)bn * a.H + h) * g.m;
+  w.lse = a.lse + soff;
+  w.delta = a.delta + soff;
+  w.dq = w.dk = w.dv = nullptr;
+  const int64_t goff = tok0 * ((int64_t)a.H * D) + h * D;
+  w.gq = a.gq + goff; w.gk = a.gk + goff; w.gv = a.gv + goff;
+  w.rs = a.row_stride * g.r;
+  w.rso = (int64_t)a.H * D;
+  w.grs = (int64_t)a.H * D * g.r;
+  w.nk = gp_valid_rows(g, a.L, n, j);
+  const int64_t lim = a.L - ((int64_t)n * g.g + j);                      // merge slots n g + i r + j < L
+  const int64_t nq = lim > 0 ? (lim + g.r - 1) / g.r : 0;
+  w.nq = (int)(nq < g.m ? nq : g.m);
+  w.npad = g.m - w.nk;
+}
+
+GP_DEV void add_f32x4(float* p, f32x4 v, float c) {                      // read-add-write, 16-byte aligned
+  f32x4* q = reinterpret_cast<f32x4*>(p);
+  *q = *q + v * c;
+}
 
 // Fragments of one 16-row sub-tile for the products that contract over d: lane (l16, g4) holds row l16,
 // d = 32 ks + 8 g4 .. + 7 of k-step ks; D = 48 pads its second step with zeros (lanes g4 >= 2 load nothing).
@@ -112,7 +198,8 @@ struct TileStage {
   static constexpr int LPT = 2 * kTile * CH / 256;
   static_assert((2 * kTile * CH) % 256 == 0, "two tiles must split evenly over 256 threads");
   uint4 r[LPT];
-  GP_DEV void load(const uint16_t* x0, const uint16_t* x1, int64_t rs, int row0, int L) {
+  // tile 0: rows of x0 (stride rs0, n0 valid rows), tile 1: rows of x1 (rs1, n1)
+  GP_DEV void load(const uint16_t* x0, int64_t rs0, int n0, const uint16_t* x1, int64_t rs1, int n1, int row0) {
 #pragma unroll
     for (int u = 0; u < LPT; ++u) {
       const int idx = threadIdx.x + 256 * u;
@@ -120,7 +207,8 @@ struct TileStage {
       const int rem = idx % (kTile * CH);
       const int row = rem / CH, ch = rem % CH;
       uint4 z = make_uint4(0, 0, 0, 0);
-      if (row0 + row < L) z = *reinterpret_cast<const uint4*>((tsel ? x1 : x0) + (int64_t)(row0 + row) * rs + ch * 8);
+      if (row0 + row < (tsel ? n1 : n0))
+        z = *reinterpret_cast<const uint4*>((tsel ? x1 : x0) + (int64_t)(row0 + row) * (tsel ? rs1 : rs0) + ch * 8);
       r[u] = z;
     }
   }
@@ -138,8 +226,8 @@ struct TileStage {
 
 // ---------------------------------------------------------------------------------------
 // dQ (and delta): one workgroup per 128 query rows of a (batch, head).
-template <int D, bool kH>
-__global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const BwdArgs a) {
+template <int D, bool kH, bool kDil>
+__global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const std::conditional_t<kDil, DilArgs, BwdArgs> a) {
   using TS = TileStage<D>;
   constexpr int DT = D / 16, ROWB = TS::ROWB, TILEB = TS::TILEB;
   __shared__ __attribute__((aligned(16))) char smem[4 * TILEB];   // [K0 | V0 | K1 | V1]
@@ -147,14 +235,17 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const BwdArgs a) {
   const int64_t item = xcd_group(blockIdx.x, gridDim.x);
   const int tile = (int)(item % a.ntile);
   const int64_t bh = item / a.ntile;
-  const int b = (int)(bh / a.H), h = (int)(bh % a.H);
-  const int L = a.L;
+  View vw;
+  make_view<D>(a, bh, vw);
+  const int L = vw.nk;                               // keys; the seam's seqlen
+  const int nst = vw.nk < vw.nq ? vw.nk : vw.nq;     // rows whose dq is stored
+  if constexpr (kDil)
+    if (tile * kOwn >= vw.nq || L == 0) return;      // no row with a dout here (delta is written for all of them)
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int l16 = lane & 15, g4 = lane >> 4;
-  const int64_t rs = (int64_t)a.H * D;
-  const int64_t base = ((int64_t)b * L * a.H + h) * D;
-  const uint16_t* kb = a.k + base;
-  const uint16_t* vb = a.v + base;
+  const int64_t rs = vw.rs;
+  const uint16_t* kb = vw.k;
+  const uint16_t* vb = vw.v;
   const int q0 = tile * kOwn + w * (kSub * 16);
 
   // Q / dO fragments (B operands: column = query l16), delta and lse of the wave's rows
@@ -163,19 +254,19 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const BwdArgs a) {
 #pragma unroll
   for (int qt = 0; qt < kSub; ++qt) {
     const int i = q0 + qt * 16 + l16;
-    const bool valid = i < L;
-    const int64_t off = base + (int64_t)i * rs;
-    load_rowfrag<D>(qf[qt], reinterpret_cast<const char*>(a.q + off), g4, valid);
-    load_rowfrag<D>(dof[qt], reinterpret_cast<const char*>(a.dout + off), g4, valid);
+    const bool valid = i < vw.nq;                    // carries a dout (a zero-pad query past nk: q = 0)
+    load_rowfrag<D>(qf[qt], reinterpret_cast<const char*>(vw.q + (int64_t)i * rs), g4, i < vw.nk);
+    load_rowfrag<D>(dof[qt], reinterpret_cast<const char*>(vw.dout + (int64_t)i * vw.rso), g4, valid);
     RowFrag<D> of;
-    load_rowfrag<D>(of, reinterpret_cast<const char*>(a.o + off), g4, valid);
+    load_rowfrag<D>(of, reinterpret_cast<const char*>(vw.o + (int64_t)i * vw.rso), g4, valid);
     // delta: the diagonal of O.dO^T, summed exactly as dP sums dO.V^T
     const f32x4 dd = dot_rows<D, kH>(of, dof[qt], f32x4{0.f, 0.f, 0.f, 0.f});
     const int r = l16 & 3;
     const float pick = r == 0 ? dd[0] : r == 1 ? dd[1] : r == 2 ? dd[2] : dd[3];   // lane g4 == l16 / 4 holds it
     dl[qt] = __shfl(pick, ((l16 >> 2) << 4) | l16, 64);
-    lse2[qt] = valid ? a.lse[bh * L + i] * kLog2e : INFINITY;
-    if (valid && g4 == 0) a.delta[bh * L + i] = dl[qt];
+    if constexpr (!kDil)
+      if (valid && g4 == 0) vw.delta[i] = dl[qt];
+    lse2[qt] = valid ? vw.lse[i] * kLog2e : INFINITY;
   }
 
   f32x4 acc[kSub][DT];
@@ -183,16 +274,35 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const BwdArgs a) {
   for (int qt = 0; qt < kSub; ++qt)
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) acc[qt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // kDil: delta from the forward's o carries that kernel's own error (P rounded before P.V, o rounded), and an error
+  // of delta is the same for every key of the row, so it does not average out in dq.  With the recomputed fp32 P,
+  // delta* = sum_j P_ij dP_ij over all keys (zero pads: dP = 0), so eps_i = sum_j P_ij (dP_ij - delta_i) is the error
+  // of delta_i, at no extra product: the lane sums its fp32 dS below.  dq is then corrected to first order by
+  // -eps_i sum_j P_ij k_j (pk, one more accumulator set) and delta_i + eps_i is what the dK/dV kernel gets.  One key
+  // (L = 1): dS = 0 exactly, so eps = 0 and nothing changes.  dS also enters its product as a pair of 16-bit values
+  // (the rounded dS and the rounded remainder), so that dq carries the one rounding of the store and little else:
+  // an error of dq at the largest elements is otherwise a rounding of the sum plus the operand roundings, which
+  // per-branch results (smaller numbers, finer ulps) do not show.
+  f32x4 pk[kDil ? kSub : 1][kDil ? DT : 1];
+  float eps[kSub];
+#pragma unroll
+  for (int qt = 0; qt < kSub; ++qt) eps[qt] = 0.f;
+  if constexpr (kDil) {
+#pragma unroll
+    for (int qt = 0; qt < kSub; ++qt)
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) pk[qt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
 
   TS st;
   const int ntiles = (L + kTile - 1) / kTile;
-  st.load(kb, vb, rs, 0, L);
+  st.load(kb, rs, L, vb, rs, L, 0);
   st.store(smem);
   __syncthreads();
 
   for (int t = 0; t < ntiles; ++t) {
     const int kv0 = t * kTile;
-    if (t + 1 < ntiles) st.load(kb, vb, rs, kv0 + kTile, L);
+    if (t + 1 < ntiles) st.load(kb, rs, L, vb, rs, L, kv0 + kTile);
     const char* Kb = smem + (2 * (t & 1)) * TILEB;
     const char* Vb = Kb + TILEB;
     const bool tail = kv0 + kTile > L;
@@ -211,7 +321,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const BwdArgs a) {
           dpacc[qt][kt] = dot_rows<D, kH>(vv, dof[qt], f32x4{0.f, 0.f, 0.f, 0.f});
         }
       }
-      bf16x8 dsf[kSub];
+      bf16x8 dsf[kSub], pf[kDil ? kSub : 1], dsl[kDil ? kSub : 1];
 #pragma unroll
       for (int qt = 0; qt < kSub; ++qt)
 #pragma unroll
@@ -220,29 +330,63 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const BwdArgs a) {
           for (int r = 0; r < 4; ++r) {
             float p = __builtin_amdgcn_exp2f(fmaf(sacc[qt][kt][r], a.c_log2, -lse2[qt]));
             if (tail) p = (kv0 + 32 * u + 16 * kt + 4 * g4 + r < L) ? p : 0.f;
-            dsf[qt][4 * kt + r] = f2e_slot<kH>(p * (dpacc[qt][kt][r] - dl[qt]));
+            const float ds = p * (dpacc[qt][kt][r] - dl[qt]);
+            const uint16_t dsb = f2e<kH>(ds);
+            dsf[qt][4 * kt + r] = __builtin_bit_cast(__bf16, dsb);
+            if constexpr (kDil) {
+              eps[qt] += ds;
+              pf[qt][4 * kt + r] = f2e_slot<kH>(p);
+              dsl[qt][4 * kt + r] = f2e_slot<kH>(ds - e2f<kH>(dsb));   // what the rounding of dS dropped
+            }
           }
-      // dQ^T[d][q] += K^T[d][key] . dS^T[key][q]
+      // dQ^T[d][q] += K^T[d][key] . dS^T[key][q]   (kDil: and pk^T[d][q] += K^T[d][key] . P^T[key][q])
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
         const bf16x8 kT = read_transposed<ROWB>(Kb, 32 * u, dt, l16, g4);
 #pragma unroll
-        for (int qt = 0; qt < kSub; ++qt) acc[qt][dt] = mfma32<kH>(kT, dsf[qt], acc[qt][dt]);
+        for (int qt = 0; qt < kSub; ++qt) {
+          acc[qt][dt] = mfma32<kH>(kT, dsf[qt], acc[qt][dt]);
+          if constexpr (kDil) {
+            acc[qt][dt] = mfma32<kH>(kT, dsl[qt], acc[qt][dt]);
+            pk[qt][dt] = mfma32<kH>(kT, pf[qt], pk[qt][dt]);
+          }
+        }
       }
     }
     if (t + 1 < ntiles) st.store(smem + (2 * ((t + 1) & 1)) * TILEB);
     __syncthreads();
   }
 
+  if constexpr (kDil) {
+#pragma unroll
+    for (int qt = 0; qt < kSub; ++qt) {
+      // the lanes g4 = 0..3 of a query hold its keys 4 g4 + reg of every sub-tile; the zero pads add P (0 - delta)
+      float e = eps[qt];
+      e += __shfl_xor(e, 16, 64);
+      e += __shfl_xor(e, 32, 64);
+      e -= (float)vw.npad * __builtin_amdgcn_exp2f(-lse2[qt]) * dl[qt];
+      const int i = q0 + qt * 16 + l16;
+      if (i < vw.nq && g4 == 0) vw.delta[i] = dl[qt] + e;
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) acc[qt][dt] = acc[qt][dt] - pk[qt][dt] * e;
+    }
+  }
+
 #pragma unroll
   for (int qt = 0; qt < kSub; ++qt) {
     const int i = q0 + qt * 16 + l16;
-    if (i < L) {
-      uint16_t* row = a.dq + base + (int64_t)i * rs;
+    if (i < nst) {
+      if constexpr (kDil) {
+        float* row = vw.gq + (int64_t)i * vw.grs;
 #pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        const float vv[4] = {acc[qt][dt][0] * a.c, acc[qt][dt][1] * a.c, acc[qt][dt][2] * a.c, acc[qt][dt][3] * a.c};
-        store_e<kH, 4>(row + 16 * dt + 4 * g4, vv);
+        for (int dt = 0; dt < DT; ++dt) add_f32x4(row + 16 * dt + 4 * g4, acc[qt][dt], a.c);
+      } else {
+        uint16_t* row = vw.dq + (int64_t)i * rs;
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) {
+          const float vv[4] = {acc[qt][dt][0] * a.c, acc[qt][dt][1] * a.c, acc[qt][dt][2] * a.c, acc[qt][dt][3] * a.c};
+          store_e<kH, 4>(row + 16 * dt + 4 * g4, vv);
+        }
       }
     }
   }
@@ -250,8 +394,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const BwdArgs a) {
 
 // ---------------------------------------------------------------------------------------
 // dK / dV: one workgroup per 128 keys of a (batch, head).
-template <int D, bool kH>
-__global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const BwdArgs a) {
+template <int D, bool kH, bool kDil>
+__global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const std::conditional_t<kDil, DilArgs, BwdArgs> a) {
   using TS = TileStage<D>;
   constexpr int DT = D / 16, ROWB = TS::ROWB, TILEB = TS::TILEB;
   constexpr int STATB = 2 * kTile * 4;                            // lse * log2(e) | delta of a query tile
@@ -260,16 +404,19 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const BwdArgs a) {
   const int64_t item = xcd_group(blockIdx.x, gridDim.x);
   const int tile = (int)(item % a.ntile);
   const int64_t bh = item / a.ntile;
-  const int b = (int)(bh / a.H), h = (int)(bh % a.H);
-  const int L = a.L;
+  View vw;
+  make_view<D>(a, bh, vw);
+  const int L = vw.nq;                               // query rows that carry a dout; the seam's seqlen
+  const int nkey = vw.nk;
+  if constexpr (kDil)
+    if (tile * kOwn >= nkey || L == 0) return;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int l16 = lane & 15, g4 = lane >> 4;
-  const int64_t rs = (int64_t)a.H * D;
-  const int64_t base = ((int64_t)b * L * a.H + h) * D;
-  const uint16_t* qb = a.q + base;
-  const uint16_t* dob = a.dout + base;
-  const float* lseb = a.lse + bh * L;
-  const float* delb = a.delta + bh * L;
+  const int64_t rs = vw.rs;
+  const uint16_t* qb = vw.q;
+  const uint16_t* dob = vw.dout;
+  const float* lseb = vw.lse;
+  const float* delb = vw.delta;
   const int k0 = tile * kOwn + w * (kSub * 16);
 
   // K / V fragments (B operands: column = key l16) of the wave's keys
@@ -277,9 +424,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const BwdArgs a) {
 #pragma unroll
   for (int kt = 0; kt < kSub; ++kt) {
     const int key = k0 + kt * 16 + l16;
-    const int64_t off = base + (int64_t)key * rs;
-    load_rowfrag<D>(kf[kt], reinterpret_cast<const char*>(a.k + off), g4, key < L);
-    load_rowfrag<D>(vf[kt], reinterpret_cast<const char*>(a.v + off), g4, key < L);
+    load_rowfrag<D>(kf[kt], reinterpret_cast<const char*>(vw.k + (int64_t)key * rs), g4, key < nkey);
+    load_rowfrag<D>(vf[kt], reinterpret_cast<const char*>(vw.v + (int64_t)key * rs), g4, key < nkey);
   }
 
   f32x4 dkacc[kSub][DT], dvacc[kSub][DT];
@@ -305,7 +451,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const BwdArgs a) {
   };
 
   const int ntiles = (L + kTile - 1) / kTile;
-  st.load(qb, dob, rs, 0, L);
+  st.load(qb, rs, nkey, dob, vw.rso, L, 0);          // a query row past nkey is a zero pad
   load_stat(0);
   st.store(smem);
   store_stat(0);
@@ -313,7 +459,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const BwdArgs a) {
 
   for (int t = 0; t < ntiles; ++t) {
     if (t + 1 < ntiles) {
-      st.load(qb, dob, rs, (t + 1) * kTile, L);
+      st.load(qb, rs, nkey, dob, vw.rso, L, (t + 1) * kTile);
       load_stat((t + 1) * kTile);
     }
     const char* Qb = smem + (2 * (t & 1)) * TILEB;
@@ -370,14 +516,23 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const BwdArgs a) {
 #pragma unroll
   for (int kt = 0; kt < kSub; ++kt) {
     const int key = k0 + kt * 16 + l16;
-    if (key < L) {
-      const int64_t off = base + (int64_t)key * rs;
+    if (key < nkey) {
+      if constexpr (kDil) {
+        const int64_t off = (int64_t)key * vw.grs;
 #pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        const float kk[4] = {dkacc[kt][dt][0] * a.c, dkacc[kt][dt][1] * a.c, dkacc[kt][dt][2] * a.c, dkacc[kt][dt][3] * a.c};
-        const float vv[4] = {dvacc[kt][dt][0], dvacc[kt][dt][1], dvacc[kt][dt][2], dvacc[kt][dt][3]};
-        store_e<kH, 4>(a.dk + off + 16 * dt + 4 * g4, kk);
-        store_e<kH, 4>(a.dv + off + 16 * dt + 4 * g4, vv);
+        for (int dt = 0; dt < DT; ++dt) {
+          add_f32x4(vw.gk + off + 16 * dt + 4 * g4, dkacc[kt][dt], a.c);
+          add_f32x4(vw.gv + off + 16 * dt + 4 * g4, dvacc[kt][dt], 1.f);
+        }
+      } else {
+        const int64_t off = (int64_t)key * rs;
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) {
+          const float kk[4] = {dkacc[kt][dt][0] * a.c, dkacc[kt][dt][1] * a.c, dkacc[kt][dt][2] * a.c, dkacc[kt][dt][3] * a.c};
+          const float vv[4] = {dvacc[kt][dt][0], dvacc[kt][dt][1], dvacc[kt][dt][2], dvacc[kt][dt][3]};
+          store_e<kH, 4>(vw.dk + off + 16 * dt + 4 * g4, kk);
+          store_e<kH, 4>(vw.dv + off + 16 * dt + 4 * g4, vv);
+        }
       }
     }
   }
@@ -385,11 +540,146 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const BwdArgs a) {
 
 template <int D, bool kH>
 void launch_bwd(const BwdArgs& a, unsigned grid, hipStream_t s) {
-  attn_bwd_dq_kernel<D, kH><<<grid, 256, 0, s>>>(a);
-  attn_bwd_dkv_kernel<D, kH><<<grid, 256, 0, s>>>(a);
+  attn_bwd_dq_kernel<D, kH, false><<<grid, 256, 0, s>>>(a);
+  attn_bwd_dkv_kernel<D, kH, false><<<grid, 256, 0, s>>>(a);
 }
 
 bool bwd_dim_ok(int D) { return D == 48 || D == 64 || D == 96; }
+
+// ---------------------------------------------------------------------------------------
+// Backward of the merge without its LayerNorm (DilatedAttention.scattering, dilated_attention.py:100-131), one
+// thread per (token, head): the branch weights are gp_branch_merge_ln's (uncovered or lse == 0 -> -1e8, fp32
+// softmax over the branches by v_exp_f32 / v_rcp_f32) and take no gradient (:119-124, torch.no_grad()), so the
+// sparse row (n, i, h) whose merge slot is the token receives dout_b = w_b dmerged, rounded to the format as the
+// MFMA operand it is.  Covered (token, head)s and sparse rows with a slot below L correspond one to one: every
+// dout row the attention kernels read is written here, and no row the forward left unwritten is read.
+struct MergeBwdArgs {
+  const float* lse[GP_MAX_BRANCHES];
+  uint16_t* dout[GP_MAX_BRANCHES];
+  GpBranch g[GP_MAX_BRANCHES];
+  const uint16_t* dmerged;
+  int64_t B, L;
+  int32_t H, nbranch;
+};
+
+template <int D, bool kH>
+__global__ __launch_bounds__(256) void merge_bwd_kernel(const MergeBwdArgs a) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= a.B * a.L * a.H) return;
+  const int h = (int)(idx % a.H);
+  const int64_t tok = idx / a.H;
+  const int bidx = (int)(tok / a.L), p = (int)(tok % a.L);
+  float e[GP_MAX_BRANCHES];
+  int64_t row[GP_MAX_BRANCHES];                          // of dout (rows of D)
+  bool cov[GP_MAX_BRANCHES];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int b = 0; b < GP_MAX_BRANCHES; ++b) {
+    e[b] = -1e8f; cov[b] = false; row[b] = 0;
+    if (b < a.nbranch) {
+      const GpBranch g = a.g[b];
+      const int n = p / g.g, pt = p - n * g.g;
+      const int i = pt / g.r, j = pt - i * g.r;
+      const int64_t bn = (int64_t)bidx * g.nseg + n;
+      cov[b] = h / g.hpg == j;
+      row[b] = (bn * g.m + i) * a.H + h;
+      if (cov[b]) e[b] = a.lse[b][(bn * a.H + h) * g.m + i];
+      if (!cov[b] || e[b] == 0.f) e[b] = -1e8f;            // dilated_attention.py:46
+      mx = fmaxf(mx, e[b]);
+    }
+  }
+  float wsum = 0.f;
+#pragma unroll
+  for (int b = 0; b < GP_MAX_BRANCHES; ++b)
+    if (b < a.nbranch) {
+      e[b] = __builtin_amdgcn_exp2f((e[b] - mx) * kLog2e);
+      wsum += e[b];
+    }
+  const float inv = __builtin_amdgcn_rcpf(wsum);
+  const uint16_t* dm = a.dmerged + (tok * a.H + h) * D;
+#pragma unroll
+  for (int b = 0; b < GP_MAX_BRANCHES; ++b)
+    if (b < a.nbranch && cov[b]) {
+      const float wb = e[b] * inv;
+      uint16_t* drow = a.dout[b] + row[b] * D;
+#pragma unroll
+      for (int c = 0; c < D; c += 8) {
+        float x[8];
+        load_e<kH, 8>(dm + c, x);
+        *reinterpret_cast<uint4*>(drow + c) = make_uint4(pack2e<kH>(x[0] * wb, x[1] * wb), pack2e<kH>(x[2] * wb, x[3] * wb),
+                                                         pack2e<kH>(x[4] * wb, x[5] * wb), pack2e<kH>(x[6] * wb, x[7] * wb));
+      }
+    }
+}
+
+// The one rounding of the accumulated gradients: g [rows, 3, E] fp32 planes -> dq / dk / dv rows (stride ds).
+template <bool kH>
+__global__ __launch_bounds__(256) void grad_store_kernel(const float* gq, const float* gk, const float* gv,
+                                                         uint16_t* dq, uint16_t* dk, uint16_t* dv, int64_t ds,
+                                                         int64_t rows, int E) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int cpr = E / 4;
+  if (idx >= rows * cpr) return;
+  const int64_t r = idx / cpr;
+  const int c = (int)(idx % cpr) * 4;
+  float v[4];
+  load_f32<4>(gq + r * E + c, v);
+  store_e<kH, 4>(dq + r * ds + c, v);
+  load_f32<4>(gk + r * E + c, v);
+  store_e<kH, 4>(dk + r * ds + c, v);
+  load_f32<4>(gv + r * E + c, v);
+  store_e<kH, 4>(dv + r * ds + c, v);
+}
+
+// gp_dilated_attn_bwd's workspace: per branch dout_b (16-bit) and delta_b (fp32), then the three fp32 accumulators
+struct DilWs {
+  size_t dout[GP_MAX_BRANCHES], delta[GP_MAX_BRANCHES], g[3], total;
+  GpBranch geo[GP_MAX_BRANCHES];
+};
+bool dil_ws_layout(int64_t B, int64_t L, int H, int D, const int32_t* seg_len, const int32_t* ratios, int nbranch,
+                   DilWs& w) {
+  if (B <= 0 || L <= 0 || H <= 0 || H > 4096 || !bwd_dim_ok(D) || !seg_len || !ratios || nbranch < 1 ||
+      nbranch > GP_MAX_BRANCHES)
+    return false;
+  if (B > (int64_t)0x7fffffff / L) return false;            // B * L below 2^31
+  uint64_t off = 0;
+  auto take = [&](uint64_t bytes) {
+    const uint64_t at = off;
+    off += (bytes + 255) / 256 * 256;
+    return (size_t)at;
+  };
+  for (int b = 0; b < nbranch; ++b) {
+    if (seg_len[b] <= 0 || ratios[b] <= 0) return false;
+    w.geo[b] = gp_make_branch(L, seg_len[b], ratios[b], H);
+    const uint64_t rows = (uint64_t)B * w.geo[b].nseg * w.geo[b].m * H;
+    w.dout[b] = take(rows * D * sizeof(uint16_t));
+    w.delta[b] = take(rows * sizeof(float));
+  }
+  for (int i = 0; i < 3; ++i) w.g[i] = take((uint64_t)B * L * H * D * sizeof(float));
+  w.total = (size_t)off;
+  return true;
+}
+
+template <int D, bool kH>
+void launch_dil_bwd(const MergeBwdArgs& m, DilArgs a, const DilWs& w, char* ws, const uint16_t* const* o_in, int64_t B, uint16_t* dq,
+                    uint16_t* dk, uint16_t* dv, int64_t ds, hipStream_t s) {
+  const int64_t th = B * m.L * m.H;
+  merge_bwd_kernel<D, kH><<<(unsigned)((th + 255) / 256), 256, 0, s>>>(m);
+  for (int b = 0; b < m.nbranch; ++b) {                    // fixed order: each branch adds into the accumulators
+    a.g = w.geo[b];
+    a.o = o_in[b];
+    a.dout = m.dout[b];
+    a.lse = m.lse[b];
+    a.delta = reinterpret_cast<float*>(ws + w.delta[b]);
+    a.ntile = (a.g.m + kOwn - 1) / kOwn;
+    const unsigned grid = (unsigned)(B * a.g.nseg * m.H * a.ntile);
+    attn_bwd_dq_kernel<D, kH, true><<<grid, 256, 0, s>>>(a);
+    attn_bwd_dkv_kernel<D, kH, true><<<grid, 256, 0, s>>>(a);
+  }
+  const int E = m.H * D;
+  const int64_t n4 = B * m.L * (E / 4);
+  grad_store_kernel<kH><<<(unsigned)((n4 + 255) / 256), 256, 0, s>>>(a.gq, a.gk, a.gv, dq, dk, dv, ds, B * m.L, E);
+}
 
 }  // namespace
 
@@ -437,4 +727,96 @@ extern "C" int gp_seg_attn_bwd(const uint16_t* q, const uint16_t* k, const uint1
     default: if (kh) launch_bwd<96, true>(a, (unsigned)grid, s); else launch_bwd<96, false>(a, (unsigned)grid, s); break;
   }
   return gp_check_launch("gp_seg_attn_bwd");
+}
+
+extern "C" size_t gp_dilated_attn_bwd_workspace_bytes(int64_t B, int64_t L, int H, int D, const int32_t* seg_len,
+                                                      const int32_t* ratios, int nbranch) {
+  DilWs w;
+  return dil_ws_layout(B, L, H, D, seg_len, ratios, nbranch, w) ? w.total : 0;
+}
+
+extern "C" int gp_dilated_attn_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t row_stride,
+                                   int64_t B, int64_t L, int H, int D, const int32_t* seg_len, const int32_t* ratios,
+                                   int nbranch, const uint16_t* const* o_in, const float* const* lse_in,
+                                   const uint16_t* dmerged, float softmax_scale, int q_log2_prescaled, uint16_t* dq,
+                                   uint16_t* dk, uint16_t* dv, int64_t d_row_stride, void* workspace,
+                                   size_t workspace_bytes, int fmt, void* stream) {
+  GP_REQUIRE(bwd_dim_ok(D), "gp_dilated_attn_bwd: head dim %d unsupported (D in {48, 64, 96})", D);
+  GP_REQUIRE(fmt == GP_FMT_BF16 || fmt == GP_FMT_F16, "gp_dilated_attn_bwd: bad fmt %d (GP_FMT_BF16 or GP_FMT_F16)", fmt);
+  GP_REQUIRE(!q_log2_prescaled || D != 96, "gp_dilated_attn_bwd: q_log2_prescaled needs D in {48, 64} (D = %d)", D);
+  GP_REQUIRE(nbranch >= 1 && nbranch <= GP_MAX_BRANCHES, "gp_dilated_attn_bwd: nbranch must be 1..%d (got %d)",
+             GP_MAX_BRANCHES, nbranch);
+  GP_REQUIRE(B > 0 && L > 0 && H > 0 && H <= 4096 && B <= (int64_t)0x7fffffff / L,
+             "gp_dilated_attn_bwd: bad sizes B %lld, L %lld, H %d", (long long)B, (long long)L, H);
+  const void* ptrs[] = {q, k, v, dmerged, dq, dk, dv};
+  const char* names[] = {"q", "k", "v", "dmerged", "dq", "dk", "dv"};
+  for (int i = 0; i < 7; ++i) {
+    GP_REQUIRE(ptrs[i] != nullptr, "gp_dilated_attn_bwd: null pointer (%s)", names[i]);
+    GP_REQUIRE(gp_aligned(ptrs[i], 16), "gp_dilated_attn_bwd: misaligned pointer (%s)", names[i]);
+  }
+  GP_REQUIRE(seg_len && ratios && o_in && lse_in, "gp_dilated_attn_bwd: null pointer (%s)",
+             !seg_len ? "seg_len" : !ratios ? "ratios" : !o_in ? "o_in" : "lse_in");
+  const int64_t E = (int64_t)H * D;
+  GP_REQUIRE(row_stride >= E && row_stride % 8 == 0, "gp_dilated_attn_bwd: row_stride %lld below H*D = %lld or not a multiple of 8",
+             (long long)row_stride, (long long)E);
+  GP_REQUIRE(d_row_stride >= E && d_row_stride % 8 == 0,
+             "gp_dilated_attn_bwd: d_row_stride %lld below H*D = %lld or not a multiple of 8", (long long)d_row_stride,
+             (long long)E);
+  for (int b = 0; b < nbranch; ++b) {
+    GP_REQUIRE(seg_len[b] > 0 && ratios[b] > 0, "gp_dilated_attn_bwd: branch %d: bad seg_len %d / ratio %d", b,
+               seg_len[b], ratios[b]);
+    GP_REQUIRE(o_in[b] != nullptr && lse_in[b] != nullptr, "gp_dilated_attn_bwd: null pointer (o_in / lse_in [%d])", b);
+    GP_REQUIRE(gp_aligned(o_in[b], 16) && gp_aligned(lse_in[b], 4),
+               "gp_dilated_attn_bwd: misaligned pointer (o_in / lse_in [%d])", b);
+  }
+  DilWs w;
+  GP_REQUIRE(dil_ws_layout(B, L, H, D, seg_len, ratios, nbranch, w), "gp_dilated_attn_bwd: bad shape");
+  GP_REQUIRE(workspace != nullptr && workspace_bytes >= w.total,
+             "gp_dilated_attn_bwd: workspace too small (%zu bytes, gp_dilated_attn_bwd_workspace_bytes asks %zu)",
+             workspace ? workspace_bytes : (size_t)0, w.total);
+  GP_REQUIRE(gp_aligned(workspace, 16), "gp_dilated_attn_bwd: misaligned workspace (16 bytes)");
+  for (int b = 0; b < nbranch; ++b) {
+    const int64_t items = B * w.geo[b].nseg * H * ((w.geo[b].m + kOwn - 1) / kOwn);
+    GP_REQUIRE(items < (int64_t)0x7fffffff, "gp_dilated_attn_bwd: branch %d: %lld work items exceed one launch", b,
+               (long long)items);
+  }
+  GP_REQUIRE((B * L * H + 255) / 256 < (int64_t)0x7fffffff && (B * L * (E / 4) + 255) / 256 < (int64_t)0x7fffffff,
+             "gp_dilated_attn_bwd: B*L*H*D too large for one launch");
+
+  char* ws = static_cast<char*>(workspace);
+  MergeBwdArgs m = {};
+  for (int b = 0; b < nbranch; ++b) {
+    m.lse[b] = lse_in[b];
+    m.dout[b] = reinterpret_cast<uint16_t*>(ws + w.dout[b]);
+    m.g[b] = w.geo[b];
+  }
+  m.dmerged = dmerged;
+  m.B = B; m.L = L; m.H = H; m.nbranch = nbranch;
+  DilArgs a = {};
+  a.q = q; a.k = k; a.v = v;
+  a.gq = reinterpret_cast<float*>(ws + w.g[0]);
+  a.gk = reinterpret_cast<float*>(ws + w.g[1]);
+  a.gv = reinterpret_cast<float*>(ws + w.g[2]);
+  a.row_stride = row_stride; a.L = L; a.H = H;
+  if (q_log2_prescaled) {            // logits are q'.k in the log2 domain: dq' = ln 2 dS k, dk = ln 2 dS^T q'
+    a.c = 0.6931471805599453f;
+    a.c_log2 = 1.f;
+  } else {
+    a.c = softmax_scale > 0.f ? softmax_scale : 1.0f / sqrtf((float)D);
+    a.c_log2 = a.c * kLog2e;
+  }
+  hipStream_t s = gp_stream(stream);
+  // the accumulators start at zero: a (token, head) no branch covers keeps it
+  const hipError_t me = hipMemsetAsync(ws + w.g[0], 0, w.total - w.g[0], s);
+  if (me != hipSuccess) {
+    gp_set_error("gp_dilated_attn_bwd: hipMemsetAsync: %s", hipGetErrorString(me));
+    return (int)me;
+  }
+  const bool kh = fmt == GP_FMT_F16;
+  switch (D) {
+    case 48: if (kh) launch_dil_bwd<48, true>(m, a, w, ws, o_in, B, dq, dk, dv, d_row_stride, s); else launch_dil_bwd<48, false>(m, a, w, ws, o_in, B, dq, dk, dv, d_row_stride, s); break;
+    case 64: if (kh) launch_dil_bwd<64, true>(m, a, w, ws, o_in, B, dq, dk, dv, d_row_stride, s); else launch_dil_bwd<64, false>(m, a, w, ws, o_in, B, dq, dk, dv, d_row_stride, s); break;
+    default: if (kh) launch_dil_bwd<96, true>(m, a, w, ws, o_in, B, dq, dk, dv, d_row_stride, s); else launch_dil_bwd<96, false>(m, a, w, ws, o_in, B, dq, dk, dv, d_row_stride, s); break;
+  }
+  return gp_check_launch("gp_dilated_attn_bwd");
 }

@@ -59,6 +59,9 @@ SIGNATURES = {
     "gp_seg_attn_bwd_workspace_bytes": [c_i64, c_i64, c_i32, c_i32],
     "gp_seg_attn_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp,
                         ctypes.c_size_t, c_i32, c_vp],
+    "gp_dilated_attn_bwd_workspace_bytes": [c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32],
+    "gp_dilated_attn_bwd": [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
+                            c_f32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, ctypes.c_size_t, c_i32, c_vp],
     "gp_branch_merge_ln": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_i32,
                            c_vp],
     "gp_attn_rows_plan_bytes": [c_i64, c_i64, c_vp, c_vp, c_i32],
@@ -98,7 +101,8 @@ SIGNATURES = {
 }
 _RESTYPES = {"gp_last_error_string": ctypes.c_char_p, "gp_varlen_plan_bytes": c_i64, "gp_gemm_workspace_bytes": c_i64,
              "gp_cls_attn_workspace_bytes": c_i64, "gp_attn_rows_plan_bytes": c_i64,
-             "gp_seg_attn_bwd_workspace_bytes": ctypes.c_size_t}
+             "gp_seg_attn_bwd_workspace_bytes": ctypes.c_size_t,
+             "gp_dilated_attn_bwd_workspace_bytes": ctypes.c_size_t}
 
 _lib = None
 
@@ -349,7 +353,7 @@ def seg_attn_fwd(q, k, v, o, lse, softmax_scale=0.0):
     _check(fn(_ptr(q), _ptr(k), _ptr(v), nb, sl, H, D, float(softmax_scale), _ptr(o), _ptr(lse), _stream()), name)
 
 
-# gp_seg_attn_bwd's workspace (the fp32 delta): one grow-only buffer per (device, stream), so two streams never
+# gp_seg_attn_bwd's / gp_dilated_attn_bwd's workspace: one grow-only buffer per (device, stream), so two streams never
 # share it; bounded, oldest first, for callers that use a fresh stream per request
 _BWD_WS: "OrderedDict[tuple, torch.Tensor]" = OrderedDict()
 _BWD_WS_MAX = 8
@@ -384,6 +388,33 @@ def seg_attn_bwd(q, k, v, o, lse, dout, dq, dk, dv, softmax_scale=0.0):
     _check(lib.gp_seg_attn_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), _ptr(dout), nb, sl, H, D,
                                float(softmax_scale), _ptr(dq), _ptr(dk), _ptr(dv), ws.data_ptr(), ws.numel(), fmt,
                                _stream()), "gp_seg_attn_bwd")
+
+
+def dilated_attn_bwd(q, k, v, row_stride, B, L, H, D, segs, ratios, outs, lses, dmerged, dq, dk, dv, d_row_stride,
+                     softmax_scale=0.0, q_log2_prescaled=False):
+    """Backward of dilated_attn_fwd + the no-LN branch_merge_ln (gp_dilated_attn_bwd).  q / k / v: the forward's
+    (views of a fused qkv allowed); outs / lses: its per-branch outputs; dmerged [B*L, H*D] contiguous; dq / dk /
+    dv: views whose rows are d_row_stride elements apart (a fused [B*L, 3E] dqkv), all in q's 16-bit dtype."""
+    lib = load_library()
+    fmt = fmt_of(q.dtype)
+    for nm, t in (("q", q), ("k", k), ("v", v), ("dq", dq), ("dk", dk), ("dv", dv)):
+        if not t.is_cuda or t.dtype != q.dtype:
+            raise TypeError("dilated_attn_bwd: %s must be a device tensor of q's 16-bit dtype" % nm)
+    _dev(dmerged, q.dtype, "dmerged")
+    if dmerged.numel() != B * L * H * D:
+        raise ValueError("dilated_attn_bwd: dmerged holds %d elements, expected %d" % (dmerged.numel(), B * L * H * D))
+    if len(outs) != len(segs) or len(lses) != len(segs) or len(ratios) != len(segs):
+        raise ValueError("dilated_attn_bwd: one o / lse / ratio per segment length")
+    for o, l in zip(outs, lses):
+        _dev(o, q.dtype, "o")
+        _dev(l, torch.float32, "lse")
+    sa, ra = _i32_array(segs), _i32_array(ratios)
+    need = int(lib.gp_dilated_attn_bwd_workspace_bytes(B, L, H, D, sa, ra, len(segs)))
+    ws = _bwd_workspace(q.device, max(need, 256))
+    _check(lib.gp_dilated_attn_bwd(_ptr(q), _ptr(k), _ptr(v), row_stride, B, L, H, D, sa, ra, len(segs),
+                                   _ptr_array(outs), _ptr_array(lses), _ptr(dmerged), float(softmax_scale),
+                                   int(bool(q_log2_prescaled)), _ptr(dq), _ptr(dk), _ptr(dv), d_row_stride,
+                                   ws.data_ptr(), ws.numel(), fmt, _stream()), "gp_dilated_attn_bwd")
 
 
 def branch_merge_ln(outs, lses, segs, ratios, B, L, H, D, ln_w, ln_b, eps, out):

@@ -574,6 +574,55 @@ def dilated_attention_core(pa: PackedAttention, qkv: torch.Tensor, B: int, L: in
                              pa.ln_w if inner_ln else None, pa.ln_b if inner_ln else None, pa.ln_eps, out)
 
 
+class _DilatedAttentionGrad(torch.autograd.Function):
+    """merged = merge(gp_dilated_attn_fwd(qkv)) without the inner LN, differentiable: the backward is one
+    gp_dilated_attn_bwd call.  The per-branch o / lse are allocated per call and saved -- the
+    module's shared AttentionScratch would be overwritten by the next forward."""
+
+    @staticmethod
+    def forward(ctx, qkv, B, L, H, D, segs, ratios, prescaled, softmax_scale):
+        E = H * D
+        qkv = qkv.contiguous()
+        dev, act = qkv.device, qkv.dtype
+        outs, lses = [], []
+        for sl, r in zip(segs, ratios):
+            s, nseg, m = branch_geometry(L, sl, r)
+            outs.append(torch.empty(B * nseg * m * H * D, dtype=act, device=dev))
+            lses.append(torch.empty(B * nseg * H * m, dtype=torch.float32, device=dev))
+        merged = torch.empty(B * L, E, dtype=act, device=dev)
+        _hip.dilated_attn_fwd(qkv, qkv[:, E:], qkv[:, 2 * E:], 3 * E, B, L, H, D, segs, ratios, outs, lses,
+                              softmax_scale, prescaled)
+        _hip.branch_merge_ln(outs, lses, segs, ratios, B, L, H, D, None, None, 0.0, merged)
+        ctx.save_for_backward(qkv, *outs, *lses)
+        ctx.geom = (B, L, H, D, tuple(segs), tuple(ratios), bool(prescaled), float(softmax_scale))
+        return merged
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        B, L, H, D, segs, ratios, prescaled, softmax_scale = ctx.geom
+        E = H * D
+        qkv, rest = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        outs, lses = list(rest[:len(segs)]), list(rest[len(segs):])
+        dout = dout.to(qkv.dtype).contiguous()
+        dqkv = torch.empty_like(qkv)
+        _hip.dilated_attn_bwd(qkv, qkv[:, E:], qkv[:, 2 * E:], 3 * E, B, L, H, D, segs, ratios, outs, lses, dout,
+                              dqkv, dqkv[:, E:], dqkv[:, 2 * E:], 3 * E, softmax_scale, prescaled)
+        return (dqkv,) + (None,) * 8
+
+
+def dilated_attention_grad(qkv: torch.Tensor, B: int, L: int, H: int, D: int, segs, ratios, prescaled: bool,
+                           softmax_scale: float = 0.0) -> torch.Tensor:
+    """qkv [B*L, 3E] 16-bit (q | k | v; with prescaled, q already times D^-0.5 log2 e) -> merged [B*L, E], the LSE
+    merge of every dilation branch before inner_attn_ln, with a native backward to qkv.  The branch weights take
+    no gradient, as in the reference (dilated_attention.py:119-124)."""
+    if qkv.dtype not in _hip.ACT_DTYPES or qkv.dim() != 2 or qkv.shape != (B * L, 3 * H * D):
+        raise ValueError("dilated_attention_grad: qkv must be [B*L, 3*H*D] bf16 or fp16, got %s %s"
+                         % (tuple(qkv.shape), qkv.dtype))
+    return _DilatedAttentionGrad.apply(qkv, B, L, H, D, list(segs), list(ratios), bool(prescaled),
+                                       float(softmax_scale))
+
+
 # ------------------------------------------------------------------------------------------
 # encoder engine
 # ------------------------------------------------------------------------------------------
