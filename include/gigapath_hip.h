@@ -404,6 +404,38 @@ int gp_residual2_layernorm(float* x, const uint16_t* y1, const float* b1, const 
 int gp_gelu_layernorm(const uint16_t* h, const float* ln_w, const float* ln_b, float eps,
                       uint16_t* out, int64_t rows, int cols, int fmt, void* stream);
 
+/* ---- Backward of gp_gelu_layernorm (added under ABI 13; purely additive, the version stays 13): the gradient
+ * of y = LayerNorm(round_fmt(gelu_erf(h))) * ln_w + ln_b, the FFN's middle (feedforward_network.py:135-138:
+ * gelu(x.float()).type_as(x), then ffn_layernorm), given dy.
+ *
+ * gp_gelu_layernorm_bwd_workspace_bytes: bytes of the fp32 per-block partials of dln_w / dln_b
+ * ([blocks, 2, cols], blocks = min(ceil(rows / R), 1024), R = 2 rows per block at a time, 1 at cols = 6144);
+ * monotone in rows; 0 for rows <= 0 or an unsupported
+ * cols.  Host only.
+ *
+ * gp_gelu_layernorm_bwd: h (the saved pre-activation), dy and dh: [rows, cols] in fmt (GP_FMT_BF16 or
+ * GP_FMT_F16), contiguous, 16-byte aligned; ln_w: [cols] fp32; cols = 64 * {48, 64, 96}; rows == 0 returns 0.
+ * Each row recomputes g = round_fmt(gelu_erf(h)) and the LN mean / rstd over the rounded g with the forward's
+ * arithmetic (the forward saves nothing else), then, all in fp32,
+ *     xhat = (g - mean) rstd,  dxhat = dy ln_w,
+ *     dg = rstd (dxhat - mean_c(dxhat) - xhat mean_c(dxhat xhat)),
+ *     dh = round_fmt(dg gelu'(h)),  gelu'(h) = 0.5 (1 + erf(h / sqrt 2)) + h exp(-h^2 / 2) / sqrt(2 pi)
+ * (the rounding of g is straight-through, as autograd treats .type_as; dh is rounded once).
+ * dln_w[c] = sum_rows dy xhat and dln_b[c] = sum_rows dy, fp32 [cols], without atomics: every block writes the
+ * sums of the rows it owns to the workspace and a second kernel adds the partials in block order.  The grid and
+ * the row-to-block assignment depend on rows and cols only, so two calls, and two devices, give the same bits.
+ * dln_w and dln_b may both be NULL (a frozen LayerNorm): no partials are written and no workspace is needed;
+ * exactly one NULL is an error.  dh may be the same buffer as dy (a row is read completely before it is
+ * written); any other overlap of dh with dy, and any overlap of dh with h, is rejected.  A non-finite dy makes
+ * its row of dh and its column of dln_b non-finite and leaves the other rows finite (GradScaler relies on it).
+ * Every argument error (fmt, cols, null or misaligned pointers, a workspace that is too small, rows >= 2^31,
+ * aliasing) is rejected before any launch. */
+size_t gp_gelu_layernorm_bwd_workspace_bytes(int64_t rows, int cols);
+int gp_gelu_layernorm_bwd(const uint16_t* h, const uint16_t* dy, const float* ln_w, float eps,
+                          uint16_t* dh, float* dln_w, float* dln_b,
+                          void* workspace, size_t workspace_bytes,
+                          int64_t rows, int cols, int fmt, void* stream);
+
 /* ---- Projection GEMMs on MFMAs (nn.Linear of torchscale/component/multihead_attention.py:43-48,
  * feedforward_network.py:131-142, gigapath/slide_encoder.py:47-51).  A [M, K] and W [N, K] are
  * K-contiguous act (row strides lda / ldw), C [M, N] act (ldc); fp32 accumulation.  N % 256 == 0;

@@ -79,6 +79,9 @@ SIGNATURES = {
     "gp_residual_layernorm": [c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_i64, c_i32, c_i32, c_vp],
     "gp_residual2_layernorm": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_i64, c_i32, c_i32, c_vp],
     "gp_gelu_layernorm": [c_vp, c_vp, c_vp, c_f32, c_vp, c_i64, c_i32, c_i32, c_vp],
+    "gp_gelu_layernorm_bwd_workspace_bytes": [c_i64, c_i32],
+    "gp_gelu_layernorm_bwd": [c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_i64, c_i32, c_i32,
+                              c_vp],
     "gp_layernorm_f32": [c_vp, c_i64, c_vp, c_vp, c_f32, c_vp, c_i64, c_i32, c_vp],
     "gp_mean_tokens": [c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_vp],
     "gp_varlen_plan_bytes": [c_i32, c_i32],
@@ -102,7 +105,8 @@ SIGNATURES = {
 _RESTYPES = {"gp_last_error_string": ctypes.c_char_p, "gp_varlen_plan_bytes": c_i64, "gp_gemm_workspace_bytes": c_i64,
              "gp_cls_attn_workspace_bytes": c_i64, "gp_attn_rows_plan_bytes": c_i64,
              "gp_seg_attn_bwd_workspace_bytes": ctypes.c_size_t,
-             "gp_dilated_attn_bwd_workspace_bytes": ctypes.c_size_t}
+             "gp_dilated_attn_bwd_workspace_bytes": ctypes.c_size_t,
+             "gp_gelu_layernorm_bwd_workspace_bytes": ctypes.c_size_t}
 
 _lib = None
 
@@ -353,8 +357,9 @@ def seg_attn_fwd(q, k, v, o, lse, softmax_scale=0.0):
     _check(fn(_ptr(q), _ptr(k), _ptr(v), nb, sl, H, D, float(softmax_scale), _ptr(o), _ptr(lse), _stream()), name)
 
 
-# gp_seg_attn_bwd's / gp_dilated_attn_bwd's workspace: one grow-only buffer per (device, stream), so two streams never
-# share it; bounded, oldest first, for callers that use a fresh stream per request
+# gp_seg_attn_bwd's / gp_dilated_attn_bwd's / gp_gelu_layernorm_bwd's workspace: one grow-only buffer per
+# (device, stream), so two streams never share it; bounded, oldest first, for callers that use a fresh stream
+# per request
 _BWD_WS: "OrderedDict[tuple, torch.Tensor]" = OrderedDict()
 _BWD_WS_MAX = 8
 
@@ -516,6 +521,37 @@ def gelu_layernorm(h, ln_w, ln_b, eps, out, rows, cols):
     _dev(h, name="h"); _dev(out, h.dtype, "out")
     _check(lib.gp_gelu_layernorm(_ptr(h), _ptr(ln_w), _ptr(ln_b), eps, _ptr(out), rows, cols, fmt, _stream()),
            "gp_gelu_layernorm")
+
+
+def gelu_layernorm_bwd(h, dy, ln_w, eps, dh, dln_w=None, dln_b=None):
+    """Backward of gelu_layernorm (gp_gelu_layernorm_bwd): h (the saved pre-activation), dy and dh [rows, cols]
+    in one 16-bit format, ln_w [cols] fp32; dln_w / dln_b [cols] fp32 outputs, or both None for a frozen
+    LayerNorm.  dh may be dy.  The partials workspace is the grow-only buffer of this device and stream."""
+    lib = load_library()
+    fmt = fmt_of(h.dtype)
+    if h.dim() != 2:
+        raise ValueError("gelu_layernorm_bwd: h must be [rows, cols], got %s" % (tuple(h.shape),))
+    rows, cols = h.shape
+    _dev(h, name="h")
+    _dev(ln_w, torch.float32, "ln_w")
+    for nm, t in (("dy", dy), ("dh", dh)):
+        _dev(t, h.dtype, nm)
+        if t.shape != h.shape:
+            raise ValueError("gelu_layernorm_bwd: %s is %s, h is %s" % (nm, tuple(t.shape), tuple(h.shape)))
+    if ln_w.numel() != cols:
+        raise ValueError("gelu_layernorm_bwd: ln_w has %d elements, cols = %d" % (ln_w.numel(), cols))
+    for nm, t in (("dln_w", dln_w), ("dln_b", dln_b)):
+        if t is not None:
+            _dev(t, torch.float32, nm)
+            if t.numel() != cols:
+                raise ValueError("gelu_layernorm_bwd: %s has %d elements, cols = %d" % (nm, t.numel(), cols))
+    ws, nbytes = None, 0
+    if dln_w is not None or dln_b is not None:
+        nbytes = int(lib.gp_gelu_layernorm_bwd_workspace_bytes(rows, cols))
+        ws = _bwd_workspace(h.device, max(nbytes, 256))
+        nbytes = ws.numel()
+    _check(lib.gp_gelu_layernorm_bwd(_ptr(h), _ptr(dy), _ptr(ln_w), eps, _ptr(dh), _ptr(dln_w), _ptr(dln_b),
+                                     _ptr(ws), nbytes, rows, cols, fmt, _stream()), "gp_gelu_layernorm_bwd")
 
 
 def layernorm_f32(x, row_stride, ln_w, ln_b, eps, out, rows, cols):

@@ -4,11 +4,16 @@ used by finetune/training.py and finetune/predict.py).
 
 Same constructor and forward as the reference: ``feat_layer`` names the layer embeddings
 (``all_layer_embed=True`` outputs, 0 = the input embedding, i = after layer i) that are
-concatenated and fed to one ``nn.Linear``.  The MI355X slide encoder is inference-only, so the
-encoder is always frozen here (its parameters get ``requires_grad=False`` and it stays in
-eval mode); the linear classifier trains normally on its outputs.
+concatenated and fed to one ``nn.Linear``.  By default the encoder is frozen here (its parameters
+get ``requires_grad=False`` and it stays in eval mode) and the linear classifier trains on its outputs.
+With ``trainable=True`` (or GIGAPATH_TRAINABLE=1 in the environment, so that the reference's
+finetune/main.py runs unchanged) and ``freeze=False`` the encoder fine-tunes too: its parameters keep
+``requires_grad``, ``LongNetViT.enable_training()`` is called, ``train()`` reaches it and the forward runs
+under autograd.
 """
 from __future__ import annotations
+
+import os
 
 import torch
 from torch import nn
@@ -31,19 +36,26 @@ class ClassificationHead(nn.Module):
     def __init__(self, input_dim, latent_dim, feat_layer, n_classes=2, model_arch="gigapath_slide_enc12l768d",
                  pretrained="hf_hub:prov-gigapath/prov-gigapath", freeze=False, **kwargs):
         super().__init__()
+        trainable = bool(kwargs.pop("trainable", os.environ.get("GIGAPATH_TRAINABLE") == "1"))
         self.feat_layer = [int(x) for x in str(feat_layer).split("-")]
         self.feat_dim = len(self.feat_layer) * latent_dim
         self.slide_encoder = slide_encoder.create_model(pretrained, model_arch, in_chans=input_dim, **kwargs)
-        if not freeze:
-            print("MI355X slide encoder is inference-only: freezing it (the classifier still trains)")
-        for p in self.slide_encoder.parameters():
-            p.requires_grad = False
-        self.slide_encoder.eval()
+        self.encoder_trainable = trainable and not freeze
+        if self.encoder_trainable:
+            self.slide_encoder.enable_training()
+        else:
+            if not freeze:
+                print("MI355X slide encoder: freezing it (the classifier still trains); pass trainable=True "
+                      "to fine-tune the encoder")
+            for p in self.slide_encoder.parameters():
+                p.requires_grad = False
+            self.slide_encoder.eval()
         self.classifier = nn.Sequential(nn.Linear(self.feat_dim, n_classes))
 
     def train(self, mode: bool = True):
         super().train(mode)
-        self.slide_encoder.eval()            # the encoder never leaves eval mode
+        if not self.encoder_trainable:
+            self.slide_encoder.eval()        # a frozen encoder never leaves eval mode
         return self
 
     def forward(self, images: torch.Tensor, coords: torch.Tensor) -> torch.Tensor:
@@ -54,8 +66,11 @@ class ClassificationHead(nn.Module):
             coords = coords.unsqueeze(0)
         if images.dim() != 3:
             raise ValueError("images must be [B, N, D], got %s" % (tuple(images.shape),))
-        with torch.no_grad():
+        if self.encoder_trainable:
             embeds = self.slide_encoder(images, coords, all_layer_embed=True)
+        else:
+            with torch.no_grad():
+                embeds = self.slide_encoder(images, coords, all_layer_embed=True)
         feats = torch.cat([embeds[i] for i in self.feat_layer], dim=-1)
         feats = feats.to(self.classifier[0].weight.dtype)
         return self.classifier(feats.reshape(-1, feats.size(-1)))

@@ -32,6 +32,18 @@ def axis_table(embed_dim: int, grid_size: int) -> np.ndarray:
     return get_1d_sincos_pos_embed_from_grid(embed_dim // 2, ticks).astype(np.float32)
 
 
+def pos_rows(table, pos, grid_size: int):
+    """pos_embed[:, pos, :] (reference slide_encoder.py:200) as a torch constant from the [G, E/2] axis table:
+    two row gathers and a concat, row 0 (the CLS row) all zeros, negative indices wrapped as torch indexing does.
+    table: [G, E/2] fp32 tensor, pos: int64 tensor of any shape -> pos.shape + [E] fp32 on table's device."""
+    import torch
+    n_rows = grid_size * grid_size + 1
+    p = torch.where(pos < 0, pos + n_rows, pos)
+    q = (p - 1).clamp_(min=0)
+    rows = torch.cat([table[q % grid_size], table[torch.div(q, grid_size, rounding_mode="floor")]], dim=-1)
+    return rows * (p != 0).unsqueeze(-1).to(rows.dtype)
+
+
 def get_2d_sincos_pos_embed(embed_dim: int, grid_size: int, cls_token: bool = False) -> np.ndarray:
     """Full table, API-compatible with the reference (used only when ``model.pos_embed`` is read)."""
     half = axis_table(embed_dim, grid_size).astype(np.float64)

@@ -623,6 +623,87 @@ def dilated_attention_grad(qkv: torch.Tensor, B: int, L: int, H: int, D: int, se
                                        float(softmax_scale))
 
 
+# The training FFN's middle: gelu + ffn_layernorm as gp_gelu_layernorm / gp_gelu_layernorm_bwd (saving only the
+# pre-activation).  GIGAPATH_TRAIN_FFN_FUSED=0 selects the plain torch composition for A/B runs.
+TRAIN_FFN_FUSED = os.environ.get("GIGAPATH_TRAIN_FFN_FUSED", "1") != "0"
+GELU_LN_COLS = (3072, 4096, 6144)
+
+
+class _GeluLayerNormGrad(torch.autograd.Function):
+    """y = LayerNorm(round(gelu_erf(h))) w + b as one kernel each way; h is the only activation saved."""
+
+    @staticmethod
+    def forward(ctx, h, ln_weight, ln_bias, eps):
+        h = h.contiguous()
+        dev = h.device
+        w32, b32 = _f32(ln_weight, dev), _f32(ln_bias, dev)
+        y = torch.empty_like(h)
+        _hip.gelu_layernorm(h, w32, b32, float(eps), y, h.shape[0], h.shape[1])
+        ctx.save_for_backward(h, w32)
+        ctx.eps = float(eps)
+        ctx.param_dtypes = (ln_weight.dtype, ln_bias.dtype)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        h, w32 = ctx.saved_tensors
+        ours = dy.dtype != h.dtype or not dy.is_contiguous()
+        dy = dy.to(h.dtype).contiguous()
+        need_h, need_w, need_b = ctx.needs_input_grad[:3]
+        dw = db = None
+        if need_w or need_b:
+            dw = torch.empty(h.shape[1], dtype=torch.float32, device=h.device)
+            db = torch.empty_like(dw)
+        # dh over dy when dy is ours to overwrite (the cast / contiguous copy above): one [M, F] buffer fewer.
+        # autograd's own buffer is left alone (it may have other readers)
+        dh = dy if ours else torch.empty_like(h)
+        _hip.gelu_layernorm_bwd(h, dy, w32, ctx.eps, dh, dw, db)
+        wd, bd = ctx.param_dtypes
+        return (dh if need_h else None, dw.to(wd) if need_w else None, db.to(bd) if need_b else None, None)
+
+
+def gelu_layernorm_grad(h: torch.Tensor, ln_weight: torch.Tensor, ln_bias: torch.Tensor, eps: float) -> torch.Tensor:
+    """h [M, F] 16-bit -> y = ffn_layernorm(gelu(h.float()).type_as(h)) in h's format (feedforward_network.py:
+    135-138), differentiable in h and the two LayerNorm parameters: forward gp_gelu_layernorm into a fresh y,
+    backward one gp_gelu_layernorm_bwd call (fp32 parameter gradients cast to the parameters' dtype)."""
+    if h.dtype not in _hip.ACT_DTYPES or h.dim() != 2 or h.shape[1] not in GELU_LN_COLS:
+        raise ValueError("gelu_layernorm_grad: h must be [M, F] bf16 or fp16 with F in %s, got %s %s"
+                         % (GELU_LN_COLS, tuple(h.shape), h.dtype))
+    return _GeluLayerNormGrad.apply(h, ln_weight, ln_bias, eps)
+
+
+def gelu_layernorm_torch(h: torch.Tensor, ln_weight: torch.Tensor, ln_bias: torch.Tensor, eps: float,
+                         activation_dropout: float = 0.0, training: bool = False) -> torch.Tensor:
+    """The same function as torch ops under autograd (GIGAPATH_TRAIN_FFN_FUSED=0, widths the kernel does not
+    cover, activation dropout): gelu in fp32, rounded to h's format, [dropout,] LayerNorm in fp32, rounded."""
+    g = torch.nn.functional.gelu(h.float()).to(h.dtype)
+    if activation_dropout > 0:
+        g = torch.nn.functional.dropout(g, activation_dropout, training)
+    return torch.nn.functional.layer_norm(g.float(), (h.shape[-1],), ln_weight.float(), ln_bias.float(),
+                                          eps).to(h.dtype)
+
+
+def drop_path(x: torch.Tensor, drop_prob: float, training: bool) -> torch.Tensor:
+    """The reference's DropPath (timm's drop_path, torchscale/component/droppath.py): one Bernoulli(keep) draw per
+    batch element, the kept rows scaled by 1 / keep."""
+    if drop_prob == 0.0 or not training:
+        return x
+    keep = 1.0 - drop_prob
+    mask = x.new_empty((x.shape[0],) + (1,) * (x.dim() - 1)).bernoulli_(keep)
+    return x * (mask / keep)
+
+
+def takes_grad_path(module: torch.nn.Module, *inputs) -> bool:
+    """The opt-in rule of the trainable modules: the module's `trainable` flag, grad mode on, and an input that
+    requires grad or .train() with a parameter that does."""
+    if not getattr(module, "trainable", False) or not torch.is_grad_enabled():
+        return False
+    if any(isinstance(t, torch.Tensor) and t.requires_grad for t in inputs):
+        return True
+    return module.training and any(p.requires_grad for p in module.parameters())
+
+
 # ------------------------------------------------------------------------------------------
 # encoder engine
 # ------------------------------------------------------------------------------------------

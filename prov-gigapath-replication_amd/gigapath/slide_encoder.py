@@ -4,7 +4,7 @@ Same public surface as the reference (gigapath/slide_encoder.py:32-270): ``Patch
 ``LongNetViT`` (constructor kwargs, ``forward(x, coords, all_layer_embed=False) -> list``,
 ``coords_to_pos``, ``get_optimal_segment_length``), ``create_model(pretrained, model_arch,
 in_chans, local_dir, **kwargs)`` and the three registered architectures, with the same
-247-key state dict.  The forward is inference-only and runs on a ROCm device:
+247-key state dict.  The forward runs on a ROCm device; by default it is the inference path:
 
     patch GEMM (hipBLASLt) -> gp_coords_to_pos -> gp_posembed_cls_ln (pos add + CLS + LN1)
     -> 12 x LongNet layer (runtime.EncoderEngine) -> LN readouts (gp_layernorm_f32 /
@@ -12,6 +12,12 @@ in_chans, local_dir, **kwargs)`` and the three registered architectures, with th
 
 The 3.07 GB fp32 ``pos_embed`` buffer of the reference is replaced by its exact [G, E/2]
 factor (see pos_embed.py); ``model.pos_embed`` is still available, built lazily on the CPU.
+
+Training is opt-in: after ``model.enable_training()`` a forward under autograd (an input that requires grad, or
+``.train()`` with a parameter that does) takes an eager differentiable path -- torch GEMMs and LayerNorms around the
+native attention backward (gp_dilated_attn_bwd) and the fused GELU + LayerNorm backward (gp_gelu_layernorm_bwd),
+with the reference's dropout and drop-path.  Without the opt-in, under ``torch.no_grad()`` or in ``.eval()`` without
+a grad-requiring input, every call is the inference path, bit for bit.
 """
 from __future__ import annotations
 
@@ -23,9 +29,10 @@ from typing import Dict, List
 import numpy as np
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import _hip, runtime
-from .pos_embed import axis_table, get_2d_sincos_pos_embed
+from .pos_embed import axis_table, get_2d_sincos_pos_embed, pos_rows
 from .torchscale.model.LongNet import make_longnet_from_name
 
 _REGISTRY: Dict[str, callable] = {}
@@ -63,6 +70,8 @@ class PatchEmbed(nn.Module):
 
 class LongNetViT(nn.Module):
     """LongNet slide encoder backbone (reference gigapath/slide_encoder.py:54-223)."""
+
+    trainable = False       # opt-in to the differentiable path: enable_training()
 
     def __init__(self, in_chans=1536, embed_dim=256, depth=12, slide_ngrids=1000, tile_size=256,
                  max_wsi_size=262144, norm_layer=nn.LayerNorm, global_pool=False, dropout=0.25,
@@ -115,6 +124,15 @@ class LongNetViT(nn.Module):
 
     def disable_sequence_parallel(self):
         self._sp = None
+        return self
+
+    # ---------------------------------------------------------------- training opt-in
+    def enable_training(self, flag: bool = True):
+        """Opt this model, its encoder, every layer and every FFN in to (or out of) the differentiable path.
+        The path is taken only under autograd; inference calls are unchanged either way."""
+        for m in self.modules():
+            if hasattr(type(m), "trainable"):
+                m.trainable = bool(flag)
         return self
 
     # ---------------------------------------------------------------- init / helpers
@@ -196,7 +214,9 @@ class LongNetViT(nn.Module):
         1 (final, after encoder.layer_norm) or, with all_layer_embed, 1 + depth (embedding and
         every layer output, before encoder.layer_norm), each through self.norm; CLS row, or the
         mean over tiles when global_pool (reference :181-223, encoder.py:360-388)."""
-        self.encoder.check_eval()
+        grad_path = runtime.takes_grad_path(self, x)
+        if not grad_path:
+            self.encoder.check_eval()
         dev = self.cls_token.device
         if dev.type != "cuda" or x.device != dev or coords.device != dev:
             raise RuntimeError("LongNetViT (MI355X path): model, x and coords must be on the same ROCm device "
@@ -204,11 +224,49 @@ class LongNetViT(nn.Module):
         B, N, C = x.shape
         if coords.shape != (B, N, 2):
             raise ValueError("coords must be [B, N, 2], got %s" % (tuple(coords.shape),))
+        if grad_path:
+            if self._sp is not None and self._sp.world > 1:
+                raise RuntimeError("LongNetViT (MI355X path): training is single-device; call "
+                                   "disable_sequence_parallel() first")
+            return self._forward_grad(x, coords, all_layer_embed)
         if self._sp is not None and self._sp.world > 1:
             return self._forward_sp(x, coords, all_layer_embed)
         if self.use_hip_graphs and not runtime.TIMER.enabled:
             return self._forward_graphed(x, coords, all_layer_embed)
         return self._forward_device(x, coords, all_layer_embed, self.validate_positions)
+
+    def _forward_grad(self, x, coords, all_layer_embed):
+        """The differentiable forward (eager; no HIP graphs, no CLS / key-row tail): patch F.linear ->
+        gp_coords_to_pos -> + the pos-embed rows (a constant) -> CLS concat -> the layers on an fp32 residual
+        stream -> fp32 LayerNorm readouts."""
+        dev = self.cls_token.device
+        B, N, C = x.shape
+        E = self.embed_dim
+        act = runtime.act_dtype()
+        c = coords if coords.dtype in (torch.float32, torch.float64) else coords.float()
+        if self.validate_positions:
+            self.check_positions([c])
+        proj = self.patch_embed.proj
+        xp = F.linear(x.reshape(B * N, C).to(act), proj.weight.to(act), proj.bias.to(act)).view(B, N, E)
+        with torch.no_grad():
+            pos = self.coords_to_pos(c.detach(), self.tile_size)
+            rows = pos_rows(self._packed_top(dev)["tab"], pos, self.slide_ngrids)
+        cls = self.cls_token.float().expand(B, -1, -1)           # pos_embed row 0 is zero
+        h = torch.cat([cls, xp.float() + rows], dim=1)
+        states = [h]
+        for layer in self.encoder.layers:
+            h = layer._forward_grad(h)
+            states.append(h)
+        if not all_layer_embed:
+            ln = self.encoder.layer_norm
+            states = [h if ln is None else F.layer_norm(h, (E,), ln.weight.float(), ln.bias.float(), ln.eps)]
+        out_dtype = self.norm.weight.dtype
+        nw, nb = self.norm.weight.float(), self.norm.bias.float()
+        outs = []
+        for s in states:
+            pooled = s[:, 1:, :].mean(dim=1) if self.global_pool else s[:, 0]
+            outs.append(F.layer_norm(pooled, (E,), nw, nb, self.norm.eps).to(out_dtype))
+        return outs
 
     def _forward_graphed(self, x, coords, all_layer_embed):
         """Replay of a HIP graph holding the whole forward (~170 launches) for this input shape:

@@ -1,16 +1,22 @@
-"""LongNet encoder stack (reference: torchscale/architecture/encoder.py:25-399), eval-mode, subln.
+"""LongNet encoder stack (reference: torchscale/architecture/encoder.py:25-399), subln.
 
 Module tree and parameter names match the reference (layers.{i}.self_attn.*,
 self_attn_layer_norm, ffn.{fc1,fc2,ffn_layernorm}, final_layer_norm, layer_norm) so
 reference state dicts load unchanged.  ``Encoder.forward`` keeps the reference's signature
 and return dict; the arithmetic runs through runtime.EncoderEngine (HIP kernels + hipBLASLt).
 LongNetViT bypasses it to fuse the embedding with the first LayerNorm.
+
+EncoderLayer and Encoder are trainable on opt-in (`trainable`, set by LongNetViT.enable_training): with autograd
+live they take an eager differentiable path -- torch LayerNorms in fp32 and an fp32 residual stream around
+DilatedAttention's and FeedForwardNetwork's differentiable paths, with dropout and drop-path as in the reference
+(encoder.py:116-162).  Every other call is the inference path, unchanged.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from ... import _hip, runtime
 from ..component.dilated_attention import DilatedAttention
@@ -27,7 +33,14 @@ def _ln_to_act(x32: torch.Tensor, ln: nn.LayerNorm, out_act: torch.Tensor):
     out_act.copy_(tmp)
 
 
+def _ln_grad(x32: torch.Tensor, ln: nn.LayerNorm) -> torch.Tensor:
+    """LayerNorm of the fp32 residual stream in fp32 (differentiable path)."""
+    return F.layer_norm(x32, (x32.shape[-1],), ln.weight.float(), ln.bias.float(), ln.eps)
+
+
 class EncoderLayer(nn.Module):
+    trainable = False       # opt-in to the differentiable path (LongNetViT.enable_training)
+
     def __init__(self, args, depth, is_moe_layer=False, is_encoder_decoder=False):
         super().__init__()
         if is_moe_layer or is_encoder_decoder:
@@ -48,9 +61,28 @@ class EncoderLayer(nn.Module):
         return DilatedAttention(args, embed_dim, args.encoder_attention_heads, dropout=args.attention_dropout,
                                 self_attention=True, subln=args.subln)
 
+    def _forward_grad(self, x):
+        """The differentiable path (reference encoder.py:116-162, pre-LN, alpha = 1) on an fp32 residual
+        stream: LN -> self_attn -> dropout -> drop-path -> residual -> LN -> FFN -> drop-path -> residual."""
+        if self.training and self.self_attn.dropout > 0:
+            raise RuntimeError("EncoderLayer (MI355X path): attention dropout is not implemented in training; "
+                               "set attention_dropout=0")
+        act = runtime.act_dtype()
+        res = x.float()
+        a = _ln_grad(res, self.self_attn_layer_norm).to(act)
+        a, _ = self.self_attn(a, a, a)
+        a = F.dropout(a.float(), self.dropout, self.training)
+        res = res + runtime.drop_path(a, self.drop_path_prob, self.training)
+        f = self.ffn._forward_grad(_ln_grad(res, self.final_layer_norm).to(act))
+        return res + runtime.drop_path(f.float(), self.drop_path_prob, self.training)
+
     @runtime.compute_format
     def forward(self, x, encoder_padding_mask=None, attn_mask=None, rel_pos=None, multiway_split_position=None,
                 incremental_state=None):
+        if runtime.takes_grad_path(self, x):
+            if x.device.type != "cuda":
+                raise RuntimeError("EncoderLayer (MI355X path) needs ROCm device tensors")
+            return self._forward_grad(x).to(x.dtype), None
         if self.training and (self.dropout > 0 or self.drop_path_prob > 0):
             raise RuntimeError("EncoderLayer (MI355X path) is inference-only: call .eval()")
         B, L, E = x.shape
@@ -69,6 +101,8 @@ class EncoderLayer(nn.Module):
 
 
 class Encoder(nn.Module):
+    trainable = False       # opt-in to the differentiable path (LongNetViT.enable_training)
+
     def __init__(self, args, embed_tokens=None, embed_positions=None, output_projection=None,
                  is_encoder_decoder=False, **kwargs):
         super().__init__(**kwargs)
@@ -96,7 +130,9 @@ class Encoder(nn.Module):
             raise NotImplementedError("LongNetViT feeds token_embeddings; src_tokens lookup is not on the path")
         if attn_mask is not None or incremental_state is not None:
             raise NotImplementedError("attn_mask / incremental_state are not on the slide-encoder path")
-        self.check_eval()
+        grad_path = runtime.takes_grad_path(self, token_embeddings)
+        if not grad_path:
+            self.check_eval()
         x_in = token_embeddings
         B, L, E = x_in.shape
         dev = x_in.device
@@ -112,6 +148,19 @@ class Encoder(nn.Module):
                 raise ValueError("encoder_padding_mask must be [B, L] = [%d, %d], got %s"
                                  % (B, L, tuple(encoder_padding_mask.shape)))
             x_in = x_in * (1 - encoder_padding_mask.to(dev).unsqueeze(-1).type_as(x_in))
+        if grad_path:
+            # eager, layer by layer, on an fp32 residual stream (EncoderLayer._forward_grad)
+            x = x_in.float()
+            states = [x_in] if return_all_hiddens else []
+            for layer in self.layers:
+                x = layer._forward_grad(x)
+                if return_all_hiddens:
+                    states.append(x.to(x_in.dtype))
+            if self.layer_norm is not None:
+                x = _ln_grad(x, self.layer_norm)
+            return {"encoder_out": x.to(x_in.dtype), "encoder_embedding": token_embeddings,
+                    "encoder_padding_mask": encoder_padding_mask, "encoder_states": states,
+                    "l_aux": [None] * self.num_layers}
         layers = self.engine.pack(self, dev)
         pa = layers[0].attn
         ws = self.engine.workspace(dev, B, L, E, self.args.encoder_ffn_embed_dim, pa.H, pa.segs, pa.ratios)

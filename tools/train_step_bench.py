@@ -1,0 +1,214 @@
+"""Training-step measurements of the slide encoder, fused against GIGAPATH_TRAIN_FFN_FUSED=0, in one process:
+
+  (a) op    runtime.gelu_layernorm_grad forward + backward at [M, F] (default 70,001 x 3,072), bf16 and fp16,
+            against runtime.gelu_layernorm_torch (the plain torch composition): median ms, peak MiB above what was
+            allocated before the call, and gp_gelu_layernorm_bwd alone with its achieved bytes/s over the
+            algorithmic bytes (2 bytes x M x F for each of h, dy and dh) against the 6.29 TB/s HBM rate
+  (b) step  one training step of LongNetViT at N tiles (default 70,000): forward with all_layer_embed, a scalar
+            loss, backward; the finetune defaults (dropout 0.1, drop-path 0.1), bf16 and fp16 autocast
+
+The arms alternate round by round (HIP events on the launch stream, `warmup` untimed calls of each arm first,
+median over `rounds` x `iters`).  One JSON line per (part, format).
+
+    python tools/train_step_bench.py [--parts op,step] [--M 70001] [--F 3072] [--N 70000] [--rounds 7] [--iters 3]
+                                     [--warmup 2] [--out profiles/train_step_bench.json]
+    python tools/train_step_bench.py --profile-steps 2          # fused steps only: the program of a
+                                                                # rocprofv3 --kernel-trace --stats run of its own
+    python tools/train_step_bench.py --shares KERNEL_STATS.csv  # attention / GEMM / GELU+LN / rest shares of that run
+"""
+import argparse
+import csv
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "prov-gigapath-replication_amd"))
+sys.path.insert(0, ROOT)
+
+HBM_BYTES_PER_S = 6.29e12
+
+
+def timed(fn, iters):
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def peak_of(fn):
+    import torch
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    fn()
+    torch.cuda.synchronize()
+    return (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+
+
+def ab(fused, plain, args):
+    for _ in range(args.warmup):
+        fused()
+        plain()
+    tf, tp = [], []
+    for _ in range(args.rounds):                                           # interleaved arms
+        tf.append(timed(fused, args.iters))
+        tp.append(timed(plain, args.iters))
+    mf, mp = statistics.median(tf), statistics.median(tp)
+    return {"fused_ms": round(mf, 3), "unfused_ms": round(mp, 3), "unfused_over_fused": round(mp / mf, 3),
+            "fused_ms_min_max": [round(min(tf), 3), round(max(tf), 3)],
+            "unfused_ms_min_max": [round(min(tp), 3), round(max(tp), 3)],
+            "fused_peak_mib": round(peak_of(fused), 1), "unfused_peak_mib": round(peak_of(plain), 1)}
+
+
+def bench_op(args, dt, fmt):
+    import torch
+    from gigapath import _hip, runtime
+    dev = torch.device("cuda")
+    M, F = args.M, args.F
+    g = torch.Generator(device=dev).manual_seed(M)
+    h = (1.5 * torch.randn(M, F, device=dev, generator=g)).to(dt).requires_grad_(True)
+    dy = torch.randn(M, F, device=dev, generator=g).to(dt)
+    w = torch.nn.Parameter(1.0 + 0.2 * torch.randn(F, device=dev, generator=g))
+    b = torch.nn.Parameter(0.1 * torch.randn(F, device=dev, generator=g))
+
+    def run(fn):
+        def go():
+            h.grad = w.grad = b.grad = None
+            fn(h, w, b, 1e-5).backward(dy)
+        return go
+
+    rec = {"tool": "train_step_bench", "part": "op", "fmt": fmt, "M": M, "F": F}
+    rec.update(ab(run(runtime.gelu_layernorm_grad), run(runtime.gelu_layernorm_torch), args))
+    # the backward kernel alone
+    dh, dw, db = torch.empty_like(dy), torch.empty(F, device=dev), torch.empty(F, device=dev)
+    hd, wd = h.detach(), w.detach()
+
+    def kernel():
+        _hip.gelu_layernorm_bwd(hd, dy, wd, 1e-5, dh, dw, db)
+
+    kernel()
+    tk = statistics.median(timed(kernel, args.iters) for _ in range(args.rounds))
+    nbytes = 3 * 2 * M * F
+    rec.update({"bwd_kernel_ms": round(tk, 4), "bwd_algorithmic_bytes": nbytes,
+                "bwd_bytes_per_s": round(nbytes / (tk * 1e-3), 0),
+                "bwd_share_of_hbm_rate": round(nbytes / (tk * 1e-3) / HBM_BYTES_PER_S, 3)})
+    return rec
+
+
+def make_step(args, fmt):
+    import numpy as np
+    import torch
+    import oracle as orc
+    from gigapath import slide_encoder
+    dev = torch.device("cuda")
+    cfg = orc.arch_config("gigapath_slide_enc12l768d")
+    model = slide_encoder.create_model("", "gigapath_slide_enc12l768d", 1536, dropout=0.1, drop_path_rate=0.1)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in orc.make_weights(cfg, seed=0).items()}, strict=True)
+    model = model.to(dev).enable_training().train()
+    x, coords = orc.synthetic_slide(args.N)
+    x = torch.from_numpy(np.asarray(x, dtype=np.float32)).to(dev)
+    coords = torch.from_numpy(np.asarray(coords)).to(dev)
+    model.validate_positions = False                                       # no host sync inside the timed step
+
+    def step():
+        for p in model.parameters():
+            p.grad = None
+        with torch.autocast("cuda", torch.float16, enabled=fmt == "fp16"):
+            outs = model(x, coords, all_layer_embed=True)
+        sum(o.float().square().mean() for o in outs).backward()
+
+    return step
+
+
+def bench_step(args, fmt):
+    from gigapath import runtime
+    step = make_step(args, fmt)
+
+    def arm(flag):
+        def go():
+            runtime.TRAIN_FFN_FUSED = flag
+            step()
+        return go
+
+    rec = {"tool": "train_step_bench", "part": "step", "fmt": fmt, "N": args.N, "dropout": 0.1, "drop_path": 0.1}
+    try:
+        rec.update(ab(arm(True), arm(False), args))
+    finally:
+        runtime.TRAIN_FFN_FUSED = True
+    return rec
+
+
+def shares(path):
+    """Attention / GEMM / GELU+LN / rest shares of a rocprofv3 --kernel-trace --stats kernel_stats CSV."""
+    tot, groups = 0.0, {"attention": 0.0, "gemm": 0.0, "gelu_ln": 0.0, "rest": 0.0}
+    with open(path) as f:
+        for row in csv.DictReader(f):
+            name = row.get("Name") or row.get("KernelName") or ""
+            ns = float(row.get("TotalDurationNs") or row.get("TotalDuration") or 0)
+            low = name.lower()
+            if "gelu_ln" in low:
+                key = "gelu_ln"
+            elif "attn" in low or "branch_merge" in low or "dilated" in low:
+                key = "attention"
+            elif "cijk" in low or "gemm" in low:
+                key = "gemm"
+            else:
+                key = "rest"
+            groups[key] += ns
+            tot += ns
+    return {"tool": "train_step_bench", "part": "shares", "csv": os.path.basename(path), "total_ms": round(tot / 1e6, 3),
+            **{k + "_share": round(v / tot, 4) for k, v in groups.items()}}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parts", default="op,step")
+    ap.add_argument("--M", type=int, default=70001)
+    ap.add_argument("--F", type=int, default=3072)
+    ap.add_argument("--N", type=int, default=70000)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--profile-steps", type=int, default=0)
+    ap.add_argument("--shares", default=None)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    lines = []
+    if args.shares:
+        lines.append(shares(args.shares))
+    elif args.profile_steps:
+        import torch
+        step = make_step(args, "bf16")
+        for _ in range(args.profile_steps):
+            step()
+        torch.cuda.synchronize()
+        return
+    else:
+        import torch
+        from gigapath import _hip
+        _hip.load_library()
+        for part in args.parts.split(","):
+            for dt, fmt in ((torch.bfloat16, "bf16"), (torch.float16, "fp16")):
+                rec = bench_op(args, dt, fmt) if part == "op" else bench_step(args, fmt)
+                rec["rounds"], rec["iters"], rec["warmup"] = args.rounds, args.iters, args.warmup
+                rec["device"] = torch.cuda.get_device_name(0)
+                print(json.dumps(rec), flush=True)
+                lines.append(rec)
+                torch.cuda.empty_cache()
+    if args.shares:
+        print(json.dumps(lines[0]), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a" if args.shares else "w") as f:
+            for rec in lines:
+                f.write(json.dumps(rec) + "\n")
+
+
+if __name__ == "__main__":
+    main()
