@@ -436,6 +436,60 @@ int gp_gelu_layernorm_bwd(const uint16_t* h, const uint16_t* dy, const float* ln
                           void* workspace, size_t workspace_bytes,
                           int64_t rows, int cols, int fmt, void* stream);
 
+/* ---- Training-path row kernels at the model width (added under ABI 13; purely additive, the version stays 13):
+ * the residual add with output dropout and drop-path and the LayerNorm that follows it (encoder.py:116-162),
+ * forward and backward.  cols in {768, 1024, 1536}; fmt GP_FMT_BF16 or GP_FMT_F16; every [rows, cols] buffer
+ * contiguous and 16-byte aligned; rows == 0 returns 0.
+ *
+ * gp_resid_drop_ln_fwd, per row and in fp32:
+ *     r = x + s[row / rows_per_scale] * keep(seed, row cols + col) * y / (1 - p)        (fp32, stored)
+ *     a = round_fmt(LayerNorm(r) * ln_w + ln_b)                                          (fmt, stored)
+ * x: the fp32 residual stream; y: a branch output in fmt; s: device fp32, rows / rows_per_scale drop-path factors
+ * (mask / keep of one batch element each) or NULL for 1; p in [0, 1): the dropout probability, p == 0 runs no
+ * generator; ln_w / ln_b: [cols] fp32.  Three shapes, by which pointers are NULL:
+ *   (A) add + LN: everything given.
+ *   (B) add only: ln_w, ln_b and a NULL; r alone is written.
+ *   (C) LN only:  y and r NULL; a = round_fmt(LayerNorm(x) ln_w + ln_b), x fp32 (x_is_act == 0) or in fmt
+ *                 (x_is_act != 0); s, p and seed are validated and not used.
+ * r may be x itself (a row is read completely before it is written); every other overlap of an output with an
+ * input or with the other output is rejected.  (A) gives the bits of (B) followed by (C) on its r.
+ *
+ * The dropout mask is a function of (seed, element index row cols + col, p) alone -- Philox4x32-10, key = (low,
+ * high word of seed), counter = (low, high word of index >> 2, 0, 0), output word (index & 3) serves the element,
+ * keep = word >= floor(p 2^32) -- and is not stored: the backward regenerates it.
+ * gp_dropout_keep_mask writes it as bytes (1 = kept) with the same device routine: out [rows, cols] uint8, 4-byte
+ * aligned, cols any positive multiple of 4.
+ *
+ * gp_resid_drop_ln_bwd: da [rows, cols] fmt (the gradient of a), dr_in [rows, cols] fp32 or NULL (the gradient
+ * arriving at r from the residual path), saved: the LN input the forward saw (r of (A), x of (C); fp32, or fmt with
+ * saved_is_act != 0), ln_w, and the forward's s, rows_per_scale, p and seed.  mean / rstd are recomputed from saved
+ * with the forward's arithmetic (no statistics are saved); then, all in fp32,
+ *     xhat = (saved - mean) rstd,  dxhat = da ln_w,
+ *     dx = dr_in + rstd (dxhat - mean_c(dxhat) - xhat mean_c(dxhat xhat))   (fp32; fmt, rounded once, when saved is)
+ *     dy = round_fmt(s * keep / (1 - p) * dx)                                (written when dy is given)
+ *     dln_w[c] = sum_rows da xhat,  dln_b[c] = sum_rows da                   (fp32 [cols])
+ * Shapes: (A) da, saved, ln_w, dx, dy given; (B) ln_w, da, saved and dln_* NULL, dr_in given: dy = round_fmt(s keep
+ * / (1 - p) dr_in), and dx (optional) receives dr_in unless it is dr_in; (C) dy NULL.
+ * dx may be dr_in itself; every other overlap of dx or dy with an input or with each other is rejected.
+ * dln_w / dln_b follow gp_gelu_layernorm_bwd's contract: no atomics, one [2][cols] fp32 partial per block in the
+ * workspace (gp_resid_drop_ln_bwd_workspace_bytes: blocks = min(ceil(rows / 4), 1024); monotone in rows; 0 for rows
+ * <= 0 or an unsupported cols; host only), added in block order by a second kernel; the grid depends on (rows, cols)
+ * only, so two calls, and two devices, give the same bits.  Both NULL (a frozen LayerNorm): no partials, no
+ * workspace; exactly one NULL is an error.  A non-finite da / dr_in row makes only its own row of dx / dy and its
+ * columns of the sums non-finite (GradScaler relies on it).
+ * Every argument error (fmt, cols, p outside [0, 1), rows_per_scale <= 0 with s given, rows no multiple of
+ * rows_per_scale, null or misaligned pointers, a workspace that is too small, rows >= 2^31, aliasing) is rejected
+ * before any launch. */
+int gp_resid_drop_ln_fwd(const void* x, int x_is_act, const uint16_t* y, const float* s, int64_t rows_per_scale,
+                         float p, uint64_t seed, const float* ln_w, const float* ln_b, float eps, float* r,
+                         uint16_t* a, int64_t rows, int cols, int fmt, void* stream);
+size_t gp_resid_drop_ln_bwd_workspace_bytes(int64_t rows, int cols);
+int gp_resid_drop_ln_bwd(const uint16_t* da, const float* dr_in, const void* saved, int saved_is_act,
+                         const float* ln_w, float eps, const float* s, int64_t rows_per_scale, float p,
+                         uint64_t seed, void* dx, uint16_t* dy, float* dln_w, float* dln_b, void* workspace,
+                         size_t workspace_bytes, int64_t rows, int cols, int fmt, void* stream);
+int gp_dropout_keep_mask(uint64_t seed, float p, int64_t rows, int cols, uint8_t* out, void* stream);
+
 /* ---- Projection GEMMs on MFMAs (nn.Linear of torchscale/component/multihead_attention.py:43-48,
  * feedforward_network.py:131-142, gigapath/slide_encoder.py:47-51).  A [M, K] and W [N, K] are
  * K-contiguous act (row strides lda / ldw), C [M, N] act (ldc); fp32 accumulation.  N % 256 == 0;

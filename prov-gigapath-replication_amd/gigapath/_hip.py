@@ -82,6 +82,12 @@ SIGNATURES = {
     "gp_gelu_layernorm_bwd_workspace_bytes": [c_i64, c_i32],
     "gp_gelu_layernorm_bwd": [c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_i64, c_i32, c_i32,
                               c_vp],
+    "gp_resid_drop_ln_fwd": [c_vp, c_i32, c_vp, c_vp, c_i64, c_f32, ctypes.c_uint64, c_vp, c_vp, c_f32, c_vp, c_vp,
+                             c_i64, c_i32, c_i32, c_vp],
+    "gp_resid_drop_ln_bwd_workspace_bytes": [c_i64, c_i32],
+    "gp_resid_drop_ln_bwd": [c_vp, c_vp, c_vp, c_i32, c_vp, c_f32, c_vp, c_i64, c_f32, ctypes.c_uint64, c_vp, c_vp,
+                             c_vp, c_vp, c_vp, ctypes.c_size_t, c_i64, c_i32, c_i32, c_vp],
+    "gp_dropout_keep_mask": [ctypes.c_uint64, c_f32, c_i64, c_i32, c_vp, c_vp],
     "gp_layernorm_f32": [c_vp, c_i64, c_vp, c_vp, c_f32, c_vp, c_i64, c_i32, c_vp],
     "gp_mean_tokens": [c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_vp],
     "gp_varlen_plan_bytes": [c_i32, c_i32],
@@ -106,7 +112,8 @@ _RESTYPES = {"gp_last_error_string": ctypes.c_char_p, "gp_varlen_plan_bytes": c_
              "gp_cls_attn_workspace_bytes": c_i64, "gp_attn_rows_plan_bytes": c_i64,
              "gp_seg_attn_bwd_workspace_bytes": ctypes.c_size_t,
              "gp_dilated_attn_bwd_workspace_bytes": ctypes.c_size_t,
-             "gp_gelu_layernorm_bwd_workspace_bytes": ctypes.c_size_t}
+             "gp_gelu_layernorm_bwd_workspace_bytes": ctypes.c_size_t,
+             "gp_resid_drop_ln_bwd_workspace_bytes": ctypes.c_size_t}
 
 _lib = None
 
@@ -357,7 +364,7 @@ def seg_attn_fwd(q, k, v, o, lse, softmax_scale=0.0):
     _check(fn(_ptr(q), _ptr(k), _ptr(v), nb, sl, H, D, float(softmax_scale), _ptr(o), _ptr(lse), _stream()), name)
 
 
-# gp_seg_attn_bwd's / gp_dilated_attn_bwd's / gp_gelu_layernorm_bwd's workspace: one grow-only buffer per
+# gp_seg_attn_bwd's / gp_dilated_attn_bwd's / gp_gelu_layernorm_bwd's / gp_resid_drop_ln_bwd's workspace: one grow-only buffer per
 # (device, stream), so two streams never share it; bounded, oldest first, for callers that use a fresh stream
 # per request
 _BWD_WS: "OrderedDict[tuple, torch.Tensor]" = OrderedDict()
@@ -552,6 +559,99 @@ def gelu_layernorm_bwd(h, dy, ln_w, eps, dh, dln_w=None, dln_b=None):
         nbytes = ws.numel()
     _check(lib.gp_gelu_layernorm_bwd(_ptr(h), _ptr(dy), _ptr(ln_w), eps, _ptr(dh), _ptr(dln_w), _ptr(dln_b),
                                      _ptr(ws), nbytes, rows, cols, fmt, _stream()), "gp_gelu_layernorm_bwd")
+
+
+ROWS_TRAIN_COLS = (768, 1024, 1536)
+
+
+def _rows_scale(s, rows, who):
+    """(s, rows_per_scale) of a drop-path factor vector: fp32, one entry per rows / numel consecutive rows."""
+    if s is None:
+        return None, 1
+    _dev(s, torch.float32, "s")
+    if s.numel() == 0 or rows % s.numel():
+        raise ValueError("%s: s has %d entries, rows = %d" % (who, s.numel(), rows))
+    return s, rows // s.numel()
+
+
+def resid_drop_ln_fwd(x, y, s, p, seed, ln_w, ln_b, eps, r, a):
+    """gp_resid_drop_ln_fwd: r = x + s[row // rows_per_scale] keep y / (1 - p) (fp32) and a = LN(r) ln_w + ln_b in
+    the 16-bit format.  (A) everything given; (B) ln_w = ln_b = a = None; (C) y = r = None, x fp32 or 16-bit.
+    s: [rows / rows_per_scale] fp32 or None; the format is y's, or a's when y is None."""
+    lib = load_library()
+    if x.dim() != 2:
+        raise ValueError("resid_drop_ln_fwd: x must be [rows, cols], got %s" % (tuple(x.shape),))
+    rows, cols = x.shape
+    x_is_act = x.dtype in ACT_DTYPES
+    _dev(x, None if x_is_act else torch.float32, "x")
+    ref = y if y is not None else a
+    if ref is None:
+        raise ValueError("resid_drop_ln_fwd: neither y nor a given")
+    fmt = fmt_of(ref.dtype)
+    for nm, t, dt in (("y", y, ref.dtype), ("a", a, ref.dtype), ("r", r, torch.float32)):
+        if t is not None:
+            _dev(t, dt, nm)
+            if t.shape != x.shape:
+                raise ValueError("resid_drop_ln_fwd: %s is %s, x is %s" % (nm, tuple(t.shape), tuple(x.shape)))
+    if x_is_act and x.dtype != ref.dtype:
+        raise TypeError("resid_drop_ln_fwd: x is %s, a is %s" % (x.dtype, ref.dtype))
+    for nm, t in (("ln_w", ln_w), ("ln_b", ln_b)):
+        if t is not None:
+            _dev(t, torch.float32, nm)
+            if t.numel() != cols:
+                raise ValueError("resid_drop_ln_fwd: %s has %d elements, cols = %d" % (nm, t.numel(), cols))
+    s, rps = _rows_scale(s, rows, "resid_drop_ln_fwd")
+    _check(lib.gp_resid_drop_ln_fwd(_ptr(x), int(x_is_act), _ptr(y), _ptr(s), rps, float(p), int(seed), _ptr(ln_w),
+                                    _ptr(ln_b), float(eps), _ptr(r), _ptr(a), rows, cols, fmt, _stream()),
+           "gp_resid_drop_ln_fwd")
+
+
+def resid_drop_ln_bwd(da, dr_in, saved, ln_w, eps, s, p, seed, dx, dy, dln_w=None, dln_b=None):
+    """gp_resid_drop_ln_bwd: the backward of resid_drop_ln_fwd.  da 16-bit or None, dr_in fp32 or None, saved the
+    LN input (fp32 or 16-bit) or None for (B), dx fp32 (16-bit when saved is; may be dr_in; optional for (B)), dy
+    16-bit or None; dln_w / dln_b [cols] fp32 outputs, or both None for a frozen LayerNorm.  The partials
+    workspace is the grow-only buffer of this device and stream."""
+    lib = load_library()
+    lead = next((t for t in (saved, dr_in, da) if t is not None), None)
+    if lead is None or lead.dim() != 2:
+        raise ValueError("resid_drop_ln_bwd: saved / dr_in / da must be [rows, cols]")
+    rows, cols = lead.shape
+    act = next((t.dtype for t in (da, dy) if t is not None), None)
+    if act is None:
+        raise ValueError("resid_drop_ln_bwd: neither da nor dy given")
+    fmt = fmt_of(act)
+    saved_is_act = saved is not None and saved.dtype in ACT_DTYPES
+    for nm, t, dt in (("da", da, act), ("dy", dy, act), ("dr_in", dr_in, torch.float32),
+                      ("saved", saved, act if saved_is_act else torch.float32),
+                      ("dx", dx, act if saved_is_act else torch.float32)):
+        if t is not None:
+            _dev(t, dt, nm)
+            if t.shape != lead.shape:
+                raise ValueError("resid_drop_ln_bwd: %s is %s, expected %s" % (nm, tuple(t.shape), tuple(lead.shape)))
+    for nm, t in (("ln_w", ln_w), ("dln_w", dln_w), ("dln_b", dln_b)):
+        if t is not None:
+            _dev(t, torch.float32, nm)
+            if t.numel() != cols:
+                raise ValueError("resid_drop_ln_bwd: %s has %d elements, cols = %d" % (nm, t.numel(), cols))
+    s, rps = _rows_scale(s, rows, "resid_drop_ln_bwd")
+    ws, nbytes = None, 0
+    if dln_w is not None or dln_b is not None:
+        nbytes = int(lib.gp_resid_drop_ln_bwd_workspace_bytes(rows, cols))
+        ws = _bwd_workspace(lead.device, max(nbytes, 256))
+        nbytes = ws.numel()
+    _check(lib.gp_resid_drop_ln_bwd(_ptr(da), _ptr(dr_in), _ptr(saved), int(saved_is_act), _ptr(ln_w), float(eps),
+                                    _ptr(s), rps, float(p), int(seed), _ptr(dx), _ptr(dy), _ptr(dln_w), _ptr(dln_b),
+                                    _ptr(ws), nbytes, rows, cols, fmt, _stream()), "gp_resid_drop_ln_bwd")
+
+
+def dropout_keep_mask(seed, p, rows, cols, out):
+    """gp_dropout_keep_mask: the keep mask of resid_drop_ln_fwd / _bwd for (seed, p) as bytes, out [rows, cols]
+    uint8 (1 = kept)."""
+    lib = load_library()
+    _dev(out, torch.uint8, "out")
+    if tuple(out.shape) != (rows, cols):
+        raise ValueError("dropout_keep_mask: out is %s, expected %s" % (tuple(out.shape), (rows, cols)))
+    _check(lib.gp_dropout_keep_mask(int(seed), float(p), rows, cols, _ptr(out), _stream()), "gp_dropout_keep_mask")
 
 
 def layernorm_f32(x, row_stride, ln_w, ln_b, eps, out, rows, cols):

@@ -694,6 +694,200 @@ def drop_path(x: torch.Tensor, drop_prob: float, training: bool) -> torch.Tensor
     return x * (mask / keep)
 
 
+# The training path's rows at the model width: residual add + output dropout + drop-path + the LayerNorm that
+# follows, as gp_resid_drop_ln_fwd / gp_resid_drop_ln_bwd.  Saved per call: the LN input, ln_w in fp32,
+# the drop-path factors and the dropout seed -- no mask, no statistics, no cast copies.
+# GIGAPATH_TRAIN_ROWS_FUSED=0 selects the torch composition for A/B runs.
+TRAIN_ROWS_FUSED = os.environ.get("GIGAPATH_TRAIN_ROWS_FUSED", "1") != "0"
+ROWS_TRAIN_COLS = _hip.ROWS_TRAIN_COLS
+
+
+def rows_fusable(E: int, p: float = 0.0) -> bool:
+    """Whether the fused row kernels run for width E and dropout probability p (p == 1 stays on torch)."""
+    return TRAIN_ROWS_FUSED and E in ROWS_TRAIN_COLS and 0.0 <= p < 1.0
+
+
+def drop_path_scale(B: int, drop_prob: float, training: bool, dev) -> Optional[torch.Tensor]:
+    """drop_path's per-batch-element factor mask / keep as a [B] fp32 vector (the same draw), or None for 1."""
+    if drop_prob == 0.0 or not training:
+        return None
+    keep = 1.0 - drop_prob
+    return torch.empty(B, dtype=torch.float32, device=dev).bernoulli_(keep) / keep
+
+
+def _dropout_seed(p: float) -> int:
+    """One 64-bit draw per call from torch's CPU default generator (no device sync; torch.manual_seed makes a
+    step reproducible).  No draw when there is no dropout."""
+    return int(torch.empty((), dtype=torch.int64).random_()) if p > 0 else 0
+
+
+def _own_f32(dr: torch.Tensor):
+    """dr as contiguous fp32, and whether the result is a copy of ours to overwrite (the rule of
+    _GeluLayerNormGrad.backward: autograd's own buffer is left alone, it may have other readers)."""
+    ours = dr.dtype != torch.float32 or not dr.is_contiguous()
+    return dr.float().contiguous(), ours
+
+
+class _ResidDropLnGrad(torch.autograd.Function):
+    """(r, a) = (x + s keep y / (1 - p), LayerNorm(r) w + b rounded to y's format): one kernel each way; r is the
+    only activation saved."""
+
+    @staticmethod
+    def forward(ctx, x32, y16, ln_weight, ln_bias, eps, p, seed, s):
+        x32, y16 = x32.contiguous(), y16.contiguous()
+        dev = x32.device
+        w32, b32 = _f32(ln_weight, dev), _f32(ln_bias, dev)
+        r, a = torch.empty_like(x32), torch.empty_like(y16)
+        _hip.resid_drop_ln_fwd(x32, y16, s, p, seed, w32, b32, eps, r, a)
+        ctx.save_for_backward(r, w32, s)
+        ctx.args = (float(eps), float(p), int(seed), y16.dtype)
+        ctx.param_dtypes = (ln_weight.dtype, ln_bias.dtype)
+        ctx.set_materialize_grads(False)
+        return r, a
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dr, da):
+        r, w32, s = ctx.saved_tensors
+        eps, p, seed, act = ctx.args
+        if dr is None and da is None:
+            return (None,) * 8
+        need_w, need_b = ctx.needs_input_grad[2:4]
+        dy = torch.empty(r.shape, dtype=act, device=r.device)
+        dw = db = None
+        if da is None:
+            # a was not used: the add alone (the LayerNorm takes no gradient)
+            dx, _ = _own_f32(dr)
+            _hip.resid_drop_ln_bwd(None, dx, None, None, eps, s, p, seed, None, dy)
+            need_w = need_b = False
+        else:
+            da = da.to(act).contiguous()
+            if need_w or need_b:
+                dw = torch.empty(r.shape[1], dtype=torch.float32, device=r.device)
+                db = torch.empty_like(dw)
+            # dx over dr when dr is ours to overwrite: one [M, E] fp32 buffer fewer
+            dr_in, ours = _own_f32(dr) if dr is not None else (None, False)
+            dx = dr_in if ours else torch.empty_like(r)
+            _hip.resid_drop_ln_bwd(da, dr_in, r, w32, eps, s, p, seed, dx, dy, dw, db)
+        wd, bd = ctx.param_dtypes
+        return (dx, dy, dw.to(wd) if need_w else None, db.to(bd) if need_b else None, None, None, None, None)
+
+
+class _ResidDropGrad(torch.autograd.Function):
+    """r = x + s keep y / (1 - p): one kernel each way, nothing but s and the seed saved."""
+
+    @staticmethod
+    def forward(ctx, x32, y16, p, seed, s):
+        x32, y16 = x32.contiguous(), y16.contiguous()
+        r = torch.empty_like(x32)
+        _hip.resid_drop_ln_fwd(x32, y16, s, p, seed, None, None, 0.0, r, None)
+        ctx.save_for_backward(s)
+        ctx.args = (float(p), int(seed), y16.dtype)
+        return r
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dr):
+        (s,) = ctx.saved_tensors
+        p, seed, act = ctx.args
+        dx, _ = _own_f32(dr)
+        dy = torch.empty(dx.shape, dtype=act, device=dx.device)
+        _hip.resid_drop_ln_bwd(None, dx, None, None, 0.0, s, p, seed, None, dy)
+        return dx, dy, None, None, None
+
+
+class _LayerNormActGrad(torch.autograd.Function):
+    """a = LayerNorm(x) w + b rounded to the 16-bit format, x fp32 or 16-bit: one kernel each way; x and ln_w in
+    fp32 are saved."""
+
+    @staticmethod
+    def forward(ctx, x, ln_weight, ln_bias, eps, act):
+        x = x.contiguous()
+        dev = x.device
+        w32, b32 = _f32(ln_weight, dev), _f32(ln_bias, dev)
+        a = torch.empty(x.shape, dtype=act, device=dev)
+        _hip.resid_drop_ln_fwd(x, None, None, 0.0, 0, w32, b32, eps, None, a)
+        ctx.save_for_backward(x, w32)
+        ctx.args = (float(eps), act)
+        ctx.param_dtypes = (ln_weight.dtype, ln_bias.dtype)
+        return a
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, da):
+        x, w32 = ctx.saved_tensors
+        eps, act = ctx.args
+        da = da.to(act).contiguous()
+        need_w, need_b = ctx.needs_input_grad[1:3]
+        dw = db = None
+        if need_w or need_b:
+            dw = torch.empty(x.shape[1], dtype=torch.float32, device=x.device)
+            db = torch.empty_like(dw)
+        dx = torch.empty_like(x)
+        _hip.resid_drop_ln_bwd(da, None, x, w32, eps, None, 0.0, 0, dx, None, dw, db)
+        wd, bd = ctx.param_dtypes
+        return (dx, dw.to(wd) if need_w else None, db.to(bd) if need_b else None, None, None)
+
+
+def _rows_check(who: str, x: torch.Tensor, y: Optional[torch.Tensor]):
+    if x.dim() != 2 or x.shape[1] not in ROWS_TRAIN_COLS:
+        raise ValueError("%s: x must be [M, E] with E in %s, got %s" % (who, ROWS_TRAIN_COLS, tuple(x.shape)))
+    if y is not None and (x.dtype != torch.float32 or y.dtype not in _hip.ACT_DTYPES or y.shape != x.shape):
+        raise ValueError("%s: x must be fp32 and y bf16 or fp16 of x's shape, got %s %s and %s %s"
+                         % (who, tuple(x.shape), x.dtype, tuple(y.shape), y.dtype))
+
+
+def _rows_torch_add(x32, y16, p, scale, training):
+    """Today's lines (encoder.py): dropout in fp32, drop-path, residual add."""
+    a = torch.nn.functional.dropout(y16.float(), p, training)
+    if scale is not None:
+        a = (a.view(scale.numel(), -1) * scale.view(-1, 1)).view_as(a)
+    return x32 + a
+
+
+def _ln_torch(x: torch.Tensor, ln, act: torch.dtype) -> torch.Tensor:
+    return torch.nn.functional.layer_norm(x.float(), (x.shape[-1],), ln.weight.float(), ln.bias.float(),
+                                          ln.eps).to(act)
+
+
+def resid_drop_ln_grad(x32: torch.Tensor, y16: torch.Tensor, ln, p: float, scale: Optional[torch.Tensor],
+                       training: bool):
+    """x32 [M, E] fp32 residual stream, y16 [M, E] 16-bit branch output, ln an nn.LayerNorm(E), p the output dropout
+    probability (applied when training), scale the drop-path factors of drop_path_scale ([B], M = B L) or None
+    -> (r32, a16): r = x + drop_path(dropout(y)) in fp32 and a = ln(r) rounded to y's format, differentiable in x,
+    y and the two LayerNorm parameters: one gp_resid_drop_ln_fwd call forward, one gp_resid_drop_ln_bwd call
+    backward (fp32 parameter gradients cast to the parameters' dtype).  The torch composition runs with
+    GIGAPATH_TRAIN_ROWS_FUSED=0, at other widths and at p == 1."""
+    p = float(p) if training else 0.0
+    if not rows_fusable(x32.shape[-1], p):
+        r = _rows_torch_add(x32, y16, p, scale, training)
+        return r, _ln_torch(r, ln, y16.dtype)
+    _rows_check("resid_drop_ln_grad", x32, y16)
+    return _ResidDropLnGrad.apply(x32, y16, ln.weight, ln.bias, float(ln.eps), p, _dropout_seed(p), scale)
+
+
+def resid_drop_grad(x32: torch.Tensor, y16: torch.Tensor, p: float, scale: Optional[torch.Tensor],
+                    training: bool) -> torch.Tensor:
+    """resid_drop_ln_grad without the LayerNorm: r32 alone."""
+    p = float(p) if training else 0.0
+    if not rows_fusable(x32.shape[-1], p):
+        return _rows_torch_add(x32, y16, p, scale, training)
+    _rows_check("resid_drop_grad", x32, y16)
+    return _ResidDropGrad.apply(x32, y16, p, _dropout_seed(p), scale)
+
+
+def layernorm_act_grad(x: torch.Tensor, ln, act: Optional[torch.dtype] = None) -> torch.Tensor:
+    """x [M, E] fp32 (the residual stream) or 16-bit -> ln(x) rounded to the 16-bit format (x's own; for an fp32 x,
+    act or the call's activation format), differentiable in x and the LayerNorm parameters."""
+    act = x.dtype if x.dtype in _hip.ACT_DTYPES else (act or act_dtype())
+    if not rows_fusable(x.shape[-1]):
+        return _ln_torch(x, ln, act)
+    _rows_check("layernorm_act_grad", x, None)
+    if x.dtype != torch.float32 and x.dtype not in _hip.ACT_DTYPES:
+        raise ValueError("layernorm_act_grad: x must be fp32, bf16 or fp16, got %s" % x.dtype)
+    return _LayerNormActGrad.apply(x, ln.weight, ln.bias, float(ln.eps), act)
+
+
 def takes_grad_path(module: torch.nn.Module, *inputs) -> bool:
     """The opt-in rule of the trainable modules: the module's `trainable` flag, grad mode on, and an input that
     requires grad or .train() with a parameter that does."""

@@ -33,6 +33,7 @@ import torch.nn.functional as F
 
 from . import _hip, runtime
 from .pos_embed import axis_table, get_2d_sincos_pos_embed, pos_rows
+from .torchscale.architecture.encoder import run_layers_grad
 from .torchscale.model.LongNet import make_longnet_from_name
 
 _REGISTRY: Dict[str, callable] = {}
@@ -254,9 +255,7 @@ class LongNetViT(nn.Module):
         cls = self.cls_token.float().expand(B, -1, -1)           # pos_embed row 0 is zero
         h = torch.cat([cls, xp.float() + rows], dim=1)
         states = [h]
-        for layer in self.encoder.layers:
-            h = layer._forward_grad(h)
-            states.append(h)
+        h = run_layers_grad(self.encoder.layers, h, states.append)
         if not all_layer_embed:
             ln = self.encoder.layer_norm
             states = [h if ln is None else F.layer_norm(h, (E,), ln.weight.float(), ln.bias.float(), ln.eps)]

@@ -7,9 +7,11 @@ and return dict; the arithmetic runs through runtime.EncoderEngine (HIP kernels 
 LongNetViT bypasses it to fuse the embedding with the first LayerNorm.
 
 EncoderLayer and Encoder are trainable on opt-in (`trainable`, set by LongNetViT.enable_training): with autograd
-live they take an eager differentiable path -- torch LayerNorms in fp32 and an fp32 residual stream around
-DilatedAttention's and FeedForwardNetwork's differentiable paths, with dropout and drop-path as in the reference
-(encoder.py:116-162).  Every other call is the inference path, unchanged.
+live they take an eager differentiable path -- an fp32 residual stream around DilatedAttention's and
+FeedForwardNetwork's differentiable paths, with dropout and drop-path as in the reference (encoder.py:116-162).  The
+LayerNorms, the output dropouts, drop-path and the residual adds run as the training row kernels
+(runtime.layernorm_act_grad / resid_drop_ln_grad / resid_drop_grad) at the widths they cover, and as
+torch ops in fp32 otherwise or with GIGAPATH_TRAIN_ROWS_FUSED=0.  Every other call is the inference path, unchanged.
 """
 from __future__ import annotations
 
@@ -38,6 +40,26 @@ def _ln_grad(x32: torch.Tensor, ln: nn.LayerNorm) -> torch.Tensor:
     return F.layer_norm(x32, (x32.shape[-1],), ln.weight.float(), ln.bias.float(), ln.eps)
 
 
+def run_layers_grad(layers, x, on_state=None):
+    """The chain of the layers' differentiable forwards on the fp32 residual stream x [B, L, E].  Each layer is
+    handed the next layer's self_attn_layer_norm, so that layer i's last residual add and layer i + 1's first
+    LayerNorm are one call (EncoderLayer._forward_grad); the per-layer states are the r outputs, the same bits as
+    calling the layers one by one."""
+    a = None
+    n = len(layers)
+    for i, layer in enumerate(layers):
+        if not runtime.rows_fusable(layer.embed_dim, layer.dropout if layer.training else 0.0):
+            x, a = layer._forward_grad(x), None          # the torch composition, layer by layer
+        elif i + 1 < n:
+            x, a = layer._forward_grad(x, a, layers[i + 1].self_attn_layer_norm)
+            a = a.reshape(-1, a.shape[-1])
+        else:
+            x = layer._forward_grad(x, a)
+        if on_state is not None:
+            on_state(x)
+    return x
+
+
 class EncoderLayer(nn.Module):
     trainable = False       # opt-in to the differentiable path (LongNetViT.enable_training)
 
@@ -61,20 +83,47 @@ class EncoderLayer(nn.Module):
         return DilatedAttention(args, embed_dim, args.encoder_attention_heads, dropout=args.attention_dropout,
                                 self_attention=True, subln=args.subln)
 
-    def _forward_grad(self, x):
+    def _forward_grad(self, x, a_in=None, next_ln=None):
         """The differentiable path (reference encoder.py:116-162, pre-LN, alpha = 1) on an fp32 residual
-        stream: LN -> self_attn -> dropout -> drop-path -> residual -> LN -> FFN -> drop-path -> residual."""
+        stream: LN -> self_attn -> dropout -> drop-path -> residual -> LN -> FFN -> drop-path -> residual.
+
+        At the widths the training row kernels cover (runtime.rows_fusable) the rows are three fused calls:
+        LN1 (runtime.layernorm_act_grad), attention-output dropout + drop-path + residual + LN2
+        (runtime.resid_drop_ln_grad), FFN-output dropout + drop-path + residual (runtime.resid_drop_grad).
+        A stack (run_layers_grad) hands over a_in, this layer's LN1 output computed by the previous layer's last
+        call, and next_ln, the next layer's self_attn_layer_norm: the return value is then (r, next_ln(r) in the
+        16-bit format), the same bits as the two calls apart.  Both are ignored by the torch composition."""
         if self.training and self.self_attn.dropout > 0:
             raise RuntimeError("EncoderLayer (MI355X path): attention dropout is not implemented in training; "
                                "set attention_dropout=0")
         act = runtime.act_dtype()
         res = x.float()
+        if runtime.rows_fusable(self.embed_dim, self.dropout if self.training else 0.0):
+            return self._forward_grad_fused(res, act, a_in, next_ln)
         a = _ln_grad(res, self.self_attn_layer_norm).to(act)
         a, _ = self.self_attn(a, a, a)
         a = F.dropout(a.float(), self.dropout, self.training)
         res = res + runtime.drop_path(a, self.drop_path_prob, self.training)
         f = self.ffn._forward_grad(_ln_grad(res, self.final_layer_norm).to(act))
         return res + runtime.drop_path(f.float(), self.drop_path_prob, self.training)
+
+    def _forward_grad_fused(self, res, act, a_in, next_ln):
+        B, L, E = res.shape
+        M = B * L
+        dev = res.device
+        x2 = res.reshape(M, E)
+        a = a_in if a_in is not None else runtime.layernorm_act_grad(x2, self.self_attn_layer_norm)
+        a = a.view(B, L, E)
+        y, _ = self.self_attn(a, a, a)
+        s = runtime.drop_path_scale(B, self.drop_path_prob, self.training, dev)
+        r, a2 = runtime.resid_drop_ln_grad(x2, y.reshape(M, E).to(act), self.final_layer_norm, self.dropout, s,
+                                           self.training)
+        f = self.ffn._forward_grad_core(a2)
+        s = runtime.drop_path_scale(B, self.drop_path_prob, self.training, dev)
+        if next_ln is None:
+            return runtime.resid_drop_grad(r, f, self.dropout, s, self.training).view(B, L, E)
+        r2, a_next = runtime.resid_drop_ln_grad(r, f, next_ln, self.dropout, s, self.training)
+        return r2.view(B, L, E), a_next
 
     @runtime.compute_format
     def forward(self, x, encoder_padding_mask=None, attn_mask=None, rel_pos=None, multiway_split_position=None,
@@ -152,10 +201,8 @@ class Encoder(nn.Module):
             # eager, layer by layer, on an fp32 residual stream (EncoderLayer._forward_grad)
             x = x_in.float()
             states = [x_in] if return_all_hiddens else []
-            for layer in self.layers:
-                x = layer._forward_grad(x)
-                if return_all_hiddens:
-                    states.append(x.to(x_in.dtype))
+            x = run_layers_grad(self.layers, x, (lambda r: states.append(r.to(x_in.dtype)))
+                                if return_all_hiddens else None)
             if self.layer_norm is not None:
                 x = _ln_grad(x, self.layer_norm)
             return {"encoder_out": x.to(x_in.dtype), "encoder_embedding": token_embeddings,

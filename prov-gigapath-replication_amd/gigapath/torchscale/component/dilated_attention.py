@@ -82,7 +82,10 @@ class DilatedAttention(nn.Module):
         merged = runtime.dilated_attention_grad(qkv, B, L, H, D, self.args.segment_length, self.args.dilated_ratio,
                                                 prescaled)
         ln = self.inner_attn_ln
-        a = F.layer_norm(merged.float(), (E,), ln.weight.float(), ln.bias.float(), ln.eps).to(act)
+        if runtime.rows_fusable(E):
+            a = runtime.layernorm_act_grad(merged, ln)        # one kernel each way, merged the only tensor saved
+        else:
+            a = F.layer_norm(merged.float(), (E,), ln.weight.float(), ln.bias.float(), ln.eps).to(act)
         out = F.linear(a, self.out_proj.weight.to(act), self.out_proj.bias.to(act))
         return out.view(B, L, E).to(query.dtype), None
 

@@ -33,8 +33,9 @@ class FeedForwardNetwork(nn.Module):
         self.fc2 = nn.Linear(ffn_dim, embed_dim)
         self.ffn_layernorm = nn.LayerNorm(ffn_dim, eps=layernorm_eps)
 
-    def _forward_grad(self, x):
-        """The differentiable path (reference feedforward_network.py:131-142): the fused middle when there is
+    def _forward_grad_core(self, x):
+        """The differentiable path before the output dropout, in the activation format (the encoder layer fuses
+        that dropout into its residual add).  Reference feedforward_network.py:131-142: the fused middle when there is
         no activation dropout, GIGAPATH_TRAIN_FFN_FUSED is on and the width is one the kernel covers; otherwise
         the torch composition with the activation dropout between the GELU and ffn_layernorm."""
         shape = x.shape
@@ -45,8 +46,11 @@ class FeedForwardNetwork(nn.Module):
             y = runtime.gelu_layernorm_grad(h, ln.weight, ln.bias, ln.eps)
         else:
             y = runtime.gelu_layernorm_torch(h, ln.weight, ln.bias, ln.eps, self.activation_dropout, self.training)
-        out = F.linear(y, self.fc2.weight.to(act), self.fc2.bias.to(act)).view(shape)
-        return F.dropout(out, self.dropout, self.training).to(x.dtype)
+        return F.linear(y, self.fc2.weight.to(act), self.fc2.bias.to(act)).view(shape)
+
+    def _forward_grad(self, x):
+        """The differentiable path with the output dropout (standalone calls, and the layer's torch composition)."""
+        return F.dropout(self._forward_grad_core(x), self.dropout, self.training).to(x.dtype)
 
     @runtime.compute_format
     def forward(self, x):

@@ -1,20 +1,26 @@
-"""Training-step measurements of the slide encoder, fused against GIGAPATH_TRAIN_FFN_FUSED=0, in one process:
+"""Training-step measurements of the slide encoder, fused against GIGAPATH_TRAIN_FFN_FUSED=0 and against
+GIGAPATH_TRAIN_ROWS_FUSED=0, in one process:
 
   (a) op    runtime.gelu_layernorm_grad forward + backward at [M, F] (default 70,001 x 3,072), bf16 and fp16,
             against runtime.gelu_layernorm_torch (the plain torch composition): median ms, peak MiB above what was
             allocated before the call, and gp_gelu_layernorm_bwd alone with its achieved bytes/s over the
             algorithmic bytes (2 bytes x M x F for each of h, dy and dh) against the 6.29 TB/s HBM rate
   (b) step  one training step of LongNetViT at N tiles (default 70,000): forward with all_layer_embed, a scalar
-            loss, backward; the finetune defaults (dropout 0.1, drop-path 0.1), bf16 and fp16 autocast
+            loss, backward; the finetune defaults (dropout 0.1, drop-path 0.1), bf16 and fp16 autocast; three
+            interleaved arms: everything fused, the FFN middle on torch, the model-width rows on torch
+  (c) rows  runtime.resid_drop_ln_grad forward + backward (the add + LN call) at [M, E] (default 70,001 x 768,
+            p = 0.1, one drop-path factor) against its torch composition, and every row kernel alone (add + LN, add,
+            LN of the fp32 stream, LN of a 16-bit tensor; forward and backward; the add shapes at p = 0.1 and p = 0)
+            with its achieved bytes/s over the algorithmic bytes against the 6.29 TB/s HBM rate
 
 The arms alternate round by round (HIP events on the launch stream, `warmup` untimed calls of each arm first,
 median over `rounds` x `iters`).  One JSON line per (part, format).
 
-    python tools/train_step_bench.py [--parts op,step] [--M 70001] [--F 3072] [--N 70000] [--rounds 7] [--iters 3]
-                                     [--warmup 2] [--out profiles/train_step_bench.json]
+    python tools/train_step_bench.py [--parts op,step,rows] [--M 70001] [--F 3072] [--E 768] [--N 70000]
+                                     [--rounds 7] [--iters 3] [--warmup 2] [--out profiles/train_step_bench.json]
     python tools/train_step_bench.py --profile-steps 2          # fused steps only: the program of a
                                                                 # rocprofv3 --kernel-trace --stats run of its own
-    python tools/train_step_bench.py --shares KERNEL_STATS.csv  # attention / GEMM / GELU+LN / rest shares of that run
+    python tools/train_step_bench.py --shares KERNEL_STATS.csv  # attention / GEMM / GELU+LN / rows / rest shares
 """
 import argparse
 import csv
@@ -64,6 +70,23 @@ def ab(fused, plain, args):
             "fused_ms_min_max": [round(min(tf), 3), round(max(tf), 3)],
             "unfused_ms_min_max": [round(min(tp), 3), round(max(tp), 3)],
             "fused_peak_mib": round(peak_of(fused), 1), "unfused_peak_mib": round(peak_of(plain), 1)}
+
+
+def abn(arms, args):
+    """ab for any number of named arms, interleaved round by round: {name}_ms, {name}_ms_min_max, {name}_peak_mib."""
+    for _ in range(args.warmup):
+        for fn in arms.values():
+            fn()
+    times = {k: [] for k in arms}
+    for _ in range(args.rounds):
+        for k, fn in arms.items():
+            times[k].append(timed(fn, args.iters))
+    rec = {}
+    for k, fn in arms.items():
+        rec[k + "_ms"] = round(statistics.median(times[k]), 3)
+        rec[k + "_ms_min_max"] = [round(min(times[k]), 3), round(max(times[k]), 3)]
+        rec[k + "_peak_mib"] = round(peak_of(fn), 1)
+    return rec
 
 
 def bench_op(args, dt, fmt):
@@ -130,23 +153,82 @@ def bench_step(args, fmt):
     from gigapath import runtime
     step = make_step(args, fmt)
 
-    def arm(flag):
+    def arm(ffn, rows):
         def go():
-            runtime.TRAIN_FFN_FUSED = flag
+            runtime.TRAIN_FFN_FUSED, runtime.TRAIN_ROWS_FUSED = ffn, rows
             step()
         return go
 
     rec = {"tool": "train_step_bench", "part": "step", "fmt": fmt, "N": args.N, "dropout": 0.1, "drop_path": 0.1}
     try:
-        rec.update(ab(arm(True), arm(False), args))
+        rec.update(abn({"fused": arm(True, True), "ffn_unfused": arm(False, True), "rows_unfused": arm(True, False)},
+                       args))
     finally:
-        runtime.TRAIN_FFN_FUSED = True
+        runtime.TRAIN_FFN_FUSED = runtime.TRAIN_ROWS_FUSED = True
+    rec["rows_unfused_over_fused"] = round(rec["rows_unfused_ms"] / rec["fused_ms"], 3)
+    rec["ffn_unfused_over_fused"] = round(rec["ffn_unfused_ms"] / rec["fused_ms"], 3)
+    return rec
+
+
+def bench_rows(args, dt, fmt):
+    import torch
+    from gigapath import _hip, runtime
+    dev = torch.device("cuda")
+    M, E, p = args.M, args.E, 0.1
+    g = torch.Generator(device=dev).manual_seed(M)
+    x = torch.randn(M, E, device=dev, generator=g).requires_grad_(True)
+    y = torch.randn(M, E, device=dev, generator=g).to(dt).requires_grad_(True)
+    da = torch.randn(M, E, device=dev, generator=g).to(dt)
+    dr = torch.randn(M, E, device=dev, generator=g)
+    ln = torch.nn.LayerNorm(E, eps=1e-5).to(dev)
+    s = torch.ones(1, device=dev)
+
+    def arm(flag):
+        def go():
+            runtime.TRAIN_ROWS_FUSED = flag
+            x.grad = y.grad = ln.weight.grad = ln.bias.grad = None
+            r, a = runtime.resid_drop_ln_grad(x, y, ln, p, s, True)
+            torch.autograd.backward([r, a], [dr, da])
+        return go
+
+    rec = {"tool": "train_step_bench", "part": "rows", "fmt": fmt, "M": M, "E": E, "p": p}
+    try:
+        rec.update(abn({"fused": arm(True), "unfused": arm(False)}, args))
+    finally:
+        runtime.TRAIN_ROWS_FUSED = True
+    rec["unfused_over_fused"] = round(rec["unfused_ms"] / rec["fused_ms"], 3)
+    # every kernel alone: bytes per element read + written, by the algorithm
+    xd, yd, x16 = x.detach(), y.detach(), x.detach().to(dt)
+    w, b = ln.weight.detach(), ln.bias.detach()
+    r, a = torch.empty_like(xd), torch.empty_like(yd)
+    dx, dy, dx16 = torch.empty_like(xd), torch.empty_like(yd), torch.empty_like(yd)
+    dw, db = torch.empty(E, device=dev), torch.empty(E, device=dev)
+    kernels = {}
+    for q in (p, 0.0):
+        tag = "_p%g" % q
+        kernels["add_ln_fwd" + tag] = (12, lambda q=q: _hip.resid_drop_ln_fwd(xd, yd, s, q, 7, w, b, 1e-5, r, a))
+        kernels["add_ln_bwd" + tag] = (16, lambda q=q: _hip.resid_drop_ln_bwd(da, dr, r, w, 1e-5, s, q, 7, dx, dy, dw, db))
+        kernels["add_fwd" + tag] = (10, lambda q=q: _hip.resid_drop_ln_fwd(xd, yd, s, q, 7, None, None, 0.0, r, None))
+        kernels["add_bwd" + tag] = (6, lambda q=q: _hip.resid_drop_ln_bwd(None, dr, None, None, 0.0, s, q, 7, None, dy))
+    kernels["ln32_fwd"] = (6, lambda: _hip.resid_drop_ln_fwd(xd, None, None, 0.0, 0, w, b, 1e-5, None, a))
+    kernels["ln32_bwd"] = (10, lambda: _hip.resid_drop_ln_bwd(da, None, xd, w, 1e-5, None, 0.0, 0, dx, None, dw, db))
+    kernels["ln16_fwd"] = (4, lambda: _hip.resid_drop_ln_fwd(x16, None, None, 0.0, 0, w, b, 1e-5, None, a))
+    kernels["ln16_bwd"] = (6, lambda: _hip.resid_drop_ln_bwd(da, None, x16, w, 1e-5, None, 0.0, 0, dx16, None, dw, db))
+    rec["kernels"] = {}
+    for name, (bpe, fn) in kernels.items():
+        fn()
+        tk = statistics.median(timed(fn, args.iters) for _ in range(args.rounds))
+        nbytes = bpe * M * E
+        rec["kernels"][name] = {"ms": round(tk, 4), "bytes_per_element": bpe, "algorithmic_bytes": nbytes,
+                                "bytes_per_s": round(nbytes / (tk * 1e-3), 0),
+                                "share_of_hbm_rate": round(nbytes / (tk * 1e-3) / HBM_BYTES_PER_S, 3)}
     return rec
 
 
 def shares(path):
-    """Attention / GEMM / GELU+LN / rest shares of a rocprofv3 --kernel-trace --stats kernel_stats CSV."""
-    tot, groups = 0.0, {"attention": 0.0, "gemm": 0.0, "gelu_ln": 0.0, "rest": 0.0}
+    """Attention / GEMM / GELU+LN / model-width rows / rest shares of a rocprofv3 --kernel-trace --stats
+    kernel_stats CSV."""
+    tot, groups = 0.0, {"attention": 0.0, "gemm": 0.0, "gelu_ln": 0.0, "rows": 0.0, "rest": 0.0}
     with open(path) as f:
         for row in csv.DictReader(f):
             name = row.get("Name") or row.get("KernelName") or ""
@@ -154,6 +236,8 @@ def shares(path):
             low = name.lower()
             if "gelu_ln" in low:
                 key = "gelu_ln"
+            elif "rows_fwd_kernel" in low or "rows_bwd_" in low:
+                key = "rows"
             elif "attn" in low or "branch_merge" in low or "dilated" in low:
                 key = "attention"
             elif "cijk" in low or "gemm" in low:
@@ -171,6 +255,7 @@ def main():
     ap.add_argument("--parts", default="op,step")
     ap.add_argument("--M", type=int, default=70001)
     ap.add_argument("--F", type=int, default=3072)
+    ap.add_argument("--E", type=int, default=768)
     ap.add_argument("--N", type=int, default=70000)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=3)
@@ -195,7 +280,8 @@ def main():
         _hip.load_library()
         for part in args.parts.split(","):
             for dt, fmt in ((torch.bfloat16, "bf16"), (torch.float16, "fp16")):
-                rec = bench_op(args, dt, fmt) if part == "op" else bench_step(args, fmt)
+                rec = {"op": bench_op, "rows": bench_rows}[part](args, dt, fmt) if part != "step" \
+                    else bench_step(args, fmt)
                 rec["rounds"], rec["iters"], rec["warmup"] = args.rounds, args.iters, args.warmup
                 rec["device"] = torch.cuda.get_device_name(0)
                 print(json.dumps(rec), flush=True)
