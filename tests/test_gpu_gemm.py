@@ -13,6 +13,8 @@ pre-activation (every bf16 input value included); the statistics to 1e-5 relativ
 import pytest
 import torch
 
+import gemm_plan
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -31,6 +33,38 @@ def _rand(shape, g, scale=1.0):
 
 def _rel(got, ref):
     return ((got.float() - ref).abs().max() / ref.abs().max()).item()
+
+
+def _cus():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def _ref64(a, w, b, chunk=16384):
+    """a . w^T + b in fp64 on the 16-bit operands, and mag = |a| . |w|^T + |b| (row chunks: fp64 copies of a
+    hundred thousand rows stay small)."""
+    wd = w.double().t().contiguous()
+    wa = wd.abs()
+    bd = b.double() if b is not None else torch.zeros(w.shape[0], dtype=torch.float64, device=a.device)
+    ref = torch.empty(a.shape[0], w.shape[0], dtype=torch.float64, device=a.device)
+    mag = torch.empty_like(ref)
+    for r0 in range(0, a.shape[0], chunk):
+        ad = a[r0:r0 + chunk].double()
+        ref[r0:r0 + chunk] = ad @ wd + bd
+        mag[r0:r0 + chunk] = ad.abs() @ wa + bd.abs()
+    return ref, mag
+
+
+def _ulp(dtype):
+    return 2.0 ** -7 if dtype == torch.bfloat16 else 2.0 ** -10
+
+
+def _elem_ratio(out, ref, mag, ulp, K):
+    """max over elements of |out - ref| / bound, bound = 1.2 (ulp |ref| + K 2^-24 mag) + 1e-7: the per-element
+    bound test_ffn_fc1_gelu_and_statistics asserts of the pre-activation -- one 16-bit rounding of the output
+    plus the fp32 accumulation bound K u sum|a||w| (u = 2^-24).  A NaN or inf in out gives inf."""
+    bound = 1.2 * (ulp * ref.abs() + K * 2.0 ** -24 * mag) + 1e-7
+    r = (out.double() - ref).abs() / bound
+    return float("inf") if not torch.isfinite(r).all() else r.max().item()
 
 
 @pytest.mark.parametrize("act", ACTS)
@@ -104,8 +138,11 @@ def test_no_writes_past_row_M(M):
 @pytest.mark.parametrize("act", ACTS)
 @pytest.mark.parametrize("M", [1, 255, 1000, 70001])
 def test_ffn_fc1_gelu_and_statistics(act, M):
+    _fc1_gelu_and_statistics(act, M, 768, 3072)
+
+
+def _fc1_gelu_and_statistics(act, M, E, F):
     h = _hip()
-    E, F = 768, 3072
     g = torch.Generator(device=DEV).manual_seed(M)
     a = _rand((M, E), g).to(act)
     w1 = _rand((F, E), g, E ** -0.5 * 1.5).to(act)
@@ -180,9 +217,12 @@ def test_ffn_fc2_layernorm_fold(act, M):
     """y = fc2(ffn_layernorm(h)) from gp_ffn_fc1_gelu's h and statistics, the LN folded into fc2 as the
     engine packs it (runtime.PackedLayer), against the reference order: LN in fp32, rounded to act,
     then fc2 (+ bias) in fp32."""
+    _fc2_layernorm_fold(act, M, 768, 3072)
+
+
+def _fc2_layernorm_fold(act, M, E, F):
     from gigapath import runtime
     h = _hip()
-    E, F = 768, 3072
     g = torch.Generator(device=DEV).manual_seed(M + 1)
     a = _rand((M, E), g).to(act)
     w1 = _rand((F, E), g, E ** -0.5 * 1.5).to(act)
@@ -250,8 +290,12 @@ def _check_resid(act, x_new, xb, xst, ref_x, s, gamma, N, M):
 def test_linear_resid(act, M):
     """out-proj + residual (gp_linear_resid): x += a . w^T + b, xb, statistics; rows past M untouched; the
     split tail (70001 rows: 822 tiles) and the data-parallel plan; gamma = None updates x only."""
+    _linear_resid(act, M, 768)
+
+
+def _linear_resid(act, M, E):
     h = _hip()
-    N = K = 768
+    N = K = E
     g = torch.Generator(device=DEV).manual_seed(M + 7)
     a = _rand((M, K), g).to(act)
     w = _rand((N, K), g, K ** -0.5).to(act)
@@ -294,8 +338,12 @@ def _fold_setup(g, act, M, E, Nout):
 def test_linear_ln_fold(act, M):
     """QKV with the pre-LN folded (gp_linear_ln): against the reference order LN(x) in fp32 rounded to act,
     then x . W^T + b; the merged statistics plane and the carried shift s_out = s_in + mean'."""
+    _linear_ln_fold(act, M, 768)
+
+
+def _linear_ln_fold(act, M, E):
     h = _hip()
-    E, N = 768, 2304
+    N = 3 * E
     g = torch.Generator(device=DEV).manual_seed(M + 11)
     x, s, gam, bet, xb, st = _fold_setup(g, act, M, E, N)
     w = _rand((N, E), g, E ** -0.5).to(act)
@@ -324,8 +372,11 @@ def test_linear_ln_fold(act, M):
 def test_ffn_fc1_gelu_ln_fold(act, M):
     """fc1 + GELU with final_layer_norm folded (gp_ffn_fc1_gelu_ln) against LN(x) -> act -> fc1 -> act ->
     gelu -> act; its statistics against the kernel's own h."""
+    _fc1_gelu_ln_fold(act, M, 768, 3072)
+
+
+def _fc1_gelu_ln_fold(act, M, E, F):
     h = _hip()
-    E, F = 768, 3072
     g = torch.Generator(device=DEV).manual_seed(M + 13)
     x, s, gam, bet, xb, st = _fold_setup(g, act, M, E, F)
     w1 = _rand((F, E), g, E ** -0.5 * 1.5).to(act)
@@ -355,8 +406,11 @@ def test_ffn_fc2_ln_resid(act, M):
     """fc2 with ffn_layernorm folded + residual (gp_ffn_fc2_ln_resid): x += LN(h) . W2^T + b2 in the
     reference order (LN in fp32 rounded to act, fp32 GEMM), the next layer's xb / statistics; gamma =
     None (the last layer) updates x only."""
+    _fc2_ln_resid(act, M, 768, 3072)
+
+
+def _fc2_ln_resid(act, M, E, F):
     h = _hip()
-    E, F = 768, 3072
     g = torch.Generator(device=DEV).manual_seed(M + 17)
     hh = torch.nn.functional.gelu(_rand((M, F), g)).to(act)
     hst = torch.empty(F // 256 + 1, M, 2, device=DEV)
@@ -416,8 +470,11 @@ def test_resid_producer_merges_next_ln_stats(act, M, producer):
     """ABI 9: gp_linear_resid / gp_ffn_fc2_ln_resid with s_out merge the next LayerNorm's statistics planes
     themselves (in the split-tail reduce launch when the plan splits).  x, xb and the per-group planes equal
     the run without the merge, and the merged plane and s_out equal the consumer's own merge bit for bit."""
+    _resid_producer_merges(act, M, producer, 768, 3072)
+
+
+def _resid_producer_merges(act, M, producer, E, F):
     h = _hip()
-    E = 768
     eps = 1e-5 if producer == "out_proj" else 1e-6
     g = torch.Generator(device=DEV).manual_seed(M + 23)
     gam = 1.0 + _rand((E,), g, 0.3)
@@ -432,7 +489,7 @@ def test_resid_producer_merges_next_ln_stats(act, M, producer):
             h.linear_resid(a, w, b, xbuf, s, gam, xb, xst, ws, eps_next=eps if s_out is not None else None,
                            s_out=s_out)
     else:
-        K = 3072
+        K = F
         hh = torch.nn.functional.gelu(_rand((M, K), g)).to(act)
         hst = torch.empty(K // 256 + 1, M, 2, device=DEV)
         hf = hh.float().view(M, K // 256, 256).double()
@@ -517,7 +574,9 @@ def test_runtime_linear_takes_strided_and_offset_operands():
 def test_fp16_qkv_with_bf16_v_third(M):
     """GP_FMT_F16_VBF16 (round 5): gp_linear / gp_linear_ln of an fp16 fused QKV write the V third (columns
     [2N/3, N)) in bf16 and the rest in fp16 -- each exactly the plain fp16 launch's fp32 result rounded to
-    its format (bit-identical q / k columns; V = bf16 of the same accumulators); split tail and unsplit."""
+    its format (bit-identical q / k columns; V = bf16 of the same accumulators).  With or without a workspace
+    these row counts run the unsplit plan on 256 CUs (70,001 x 2304: 2,466 tiles, a last round of 162 > 128);
+    the split tail's reduce (its vcol0 branch) is test_gpu_gemm_plans.py's test_qkv_split_tail."""
     h = _hip()
     E, N = 768, 2304
     g = torch.Generator(device=DEV).manual_seed(M + 31)
@@ -553,3 +612,116 @@ def test_fp16_qkv_with_bf16_v_third(M):
     assert (vb - plain[:, 2 * E:].float()).abs().max().item() <= 2 ** -8 * plain[:, 2 * E:].float().abs().max().item()
     with pytest.raises(RuntimeError, match="F16_VBF16"):        # N = 512: not a fused q | k | v (N % 3 != 0)
         h.linear(a, w[:512], b[:512], torch.empty(M, 512, dtype=torch.float16, device=DEV), ws, v_bf16=True)
+
+
+# ---------------------------------------------------------------------------------------------------
+# The 24L1024d and 12L1536d archs (E = 1024 / 1536, F = 4E: K = 1024, 1536, 4096, 6144) through every epilogue:
+# the bodies above at one row, and at the smallest row count whose plan has more than one round on this
+# device -- for the GEMMs that split, the smallest split plan with a partial last row block (tests/gemm_plan.py;
+# on 256 CUs 16,497 rows for N = 1024: 260 tiles, 4 split 4 ways; 10,865 for N = 1536: 258 tiles, 2 split; 5,489 /
+# 3,697 for the 3072- / 4608-wide QKV: 264 / 270 tiles, 8 / 14 split); for fc1, whose GELU plan never splits, the
+# smallest with more than one tile on some CU (4,209 rows at F = 4096: 272 tiles; 2,673 at F = 6144: 264).
+# Each test first asserts that the plan it names is the one the library runs here.
+WIDE = [(1024, 4096), (1536, 6144)]
+
+
+def _wide_rows(h, rows, N, K, split=True):
+    """M of the row-count label, the plan asserted: "one" (a single tile), "split" (S = 4, multi-round, last
+    row block of 113 rows), "rounds" (unsplit, more tiles than CUs: the GELU plans)."""
+    G = _cus()
+    if rows == "one":
+        M = 1
+    elif split:
+        M, rem = gemm_plan.smallest_split_rows(N, K, G)
+    else:
+        M = (G // (N // 256)) * 256 + 113
+    p = gemm_plan.plan(M, N, K, G, allow_split=split)
+    assert h.gemm_workspace_bytes(M, N, K) == gemm_plan.plan(M, N, K, G).ws_bytes
+    if rows == "one":
+        assert p == (1, N // 256, 0, 0)
+    elif split:
+        assert p.S == 4 and p.rem == rem > 0 and p.n_dp >= G and p.ws_bytes > 0 and M % 256 == 113
+    else:
+        assert p.S == 1 and G < p.n_dp <= G + N // 256 and M % 256 == 113
+    return M
+
+
+@pytest.mark.parametrize("act", ACTS)
+@pytest.mark.parametrize("rows", ["one", "rounds"])
+@pytest.mark.parametrize("E,F", WIDE)
+def test_ffn_fc1_gelu_and_statistics_wide(act, rows, E, F):
+    """fc1 + GELU + statistics at K = 1024 / 1536 (N = 4096 / 6144: the non-temporal-store instantiations), and
+    its pre-activation (gp_linear, the same tiles and accumulation order) within the per-element bound."""
+    h = _hip()
+    M = _wide_rows(h, rows, F, E, split=False)
+    _fc1_gelu_and_statistics(act, M, E, F)
+    g = torch.Generator(device=DEV).manual_seed(M)          # (the operands _fc1_gelu_and_statistics drew)
+    a = _rand((M, E), g).to(act)
+    w1 = _rand((F, E), g, E ** -0.5 * 1.5).to(act)
+    b1 = _rand((F,), g, 0.2)
+    pre = torch.full((M, F), float("nan"), dtype=act, device=DEV)
+    h.linear(a, w1, b1, pre, None)
+    torch.cuda.synchronize()
+    ref, mag = _ref64(a, w1, b1)
+    ratio = _elem_ratio(pre, ref, mag, _ulp(act), E)
+    print("fc1 pre-activation %s M=%d E=%d: max |d| / bound = %.3f" % (act, M, E, ratio))
+    assert ratio <= 1.0, ratio
+
+
+@pytest.mark.parametrize("act", ACTS)
+@pytest.mark.parametrize("rows", ["one", "rounds"])
+@pytest.mark.parametrize("E,F", WIDE)
+def test_ffn_fc1_gelu_ln_fold_wide(act, rows, E, F):
+    _fc1_gelu_ln_fold(act, _wide_rows(_hip(), rows, F, E, split=False), E, F)
+
+
+@pytest.mark.parametrize("act", ACTS)
+@pytest.mark.parametrize("rows", ["one", "split"])
+@pytest.mark.parametrize("E,F", WIDE)
+def test_ffn_fc2_layernorm_fold_wide(act, rows, E, F):
+    _fc2_layernorm_fold(act, _wide_rows(_hip(), rows, E, F), E, F)
+
+
+@pytest.mark.parametrize("act", ACTS)
+@pytest.mark.parametrize("rows", ["one", "split"])
+@pytest.mark.parametrize("E,F", WIDE)
+def test_linear_resid_wide(act, rows, E, F):
+    _linear_resid(act, _wide_rows(_hip(), rows, E, E), E)
+
+
+@pytest.mark.parametrize("act", ACTS)
+@pytest.mark.parametrize("rows", ["one", "split"])
+@pytest.mark.parametrize("E,F", WIDE)
+def test_linear_ln_fold_wide(act, rows, E, F):
+    _linear_ln_fold(act, _wide_rows(_hip(), rows, 3 * E, E), E)
+
+
+@pytest.mark.parametrize("act", ACTS)
+@pytest.mark.parametrize("rows", ["one", "split"])
+@pytest.mark.parametrize("E,F", WIDE)
+def test_ffn_fc2_ln_resid_wide(act, rows, E, F):
+    _fc2_ln_resid(act, _wide_rows(_hip(), rows, E, F), E, F)
+
+
+# The producer-side merge at four (E = 1024) and six (E = 1536) statistics planes.  "whole": every tail row
+# panel entirely split (n_dp a multiple of N / 256); "mixed": the first tail panel part data-parallel, part split
+# (what 25,613 rows are for 768).  With one workgroup per CU, n_dp is a multiple of the CU count: on 256 CUs
+# N = 1024 (4 tiles per panel) has whole panels only, and for N = 1536 the smallest split plan (10,865 rows: tiles
+# 252..255 of panel 42 data-parallel, 256 and 257 split) is mixed, the smallest whole one 32,881 rows (774 tiles, 6
+# split).
+@pytest.mark.parametrize("act", ACTS)
+@pytest.mark.parametrize("E,F,rows", [(1024, 4096, "one"), (1024, 4096, "whole"), (1536, 6144, "one"),
+                                      (1536, 6144, "mixed"), (1536, 6144, "whole")])
+@pytest.mark.parametrize("producer", ["out_proj", "fc2"])
+def test_resid_producer_merges_next_ln_stats_wide(act, E, F, rows, producer):
+    h = _hip()
+    K = E if producer == "out_proj" else F
+    if rows == "one":
+        M = _wide_rows(h, rows, E, K)
+    else:
+        G = _cus()
+        M, rem = gemm_plan.panel_split_rows(E, K, G, mixed=rows == "mixed")
+        p = gemm_plan.plan(M, E, K, G)
+        assert h.gemm_workspace_bytes(M, E, K) == p.ws_bytes > 0 and p.S == 4 and p.rem == rem
+        assert (p.n_dp % (E // 256) != 0) == (rows == "mixed")
+    _resid_producer_merges(act, M, producer, E, F)
