@@ -1,6 +1,7 @@
-// Dilated attention for gfx950: sparsify (gather), per-segment flash attention with MFMA,
-// and the LSE-weighted branch merge.  Replaces DilatedAttention.gathering / flash_attn_func /
-// scattering (torchscale/component/dilated_attention.py:16-131, flash_attention.py:13-16).
+// Dilated attention forward for gfx950: per-segment flash attention with MFMA, the dilated gather folded
+// into its addressing.  Replaces DilatedAttention.gathering / flash_attn_func
+// (torchscale/component/dilated_attention.py:16-98, flash_attention.py:13-16); the LSE-weighted branch
+// merge (scattering) is gp_merge.hip, the gather / sparsify copies are gp_sparsify.hip.
 //
 // Attention kernel design (one launch covers every branch of a layer):
 //   * work item = (branch, batch*segment, head, q-block of NW*32 rows); items ordered heaviest
@@ -24,8 +25,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "gp_api.h"
-#include "gp_common.h"
+#include "gp_attn_plan.h"
 
 namespace {
 
@@ -53,55 +53,6 @@ GP_DEV f32x4 mfma_16x16x32(bf16x8 a, bf16x8 b, f32x4 c) {
 }
 template <bool kH>
 GP_DEV __bf16 f2e_slot(float f) { return __builtin_bit_cast(__bf16, f2e<kH>(f)); }
-// Exact unsigned division by a launch constant d < 2^31 via a multiply-high: the merge kernel's
-// per-token divisions are wave-uniform, so they run on the scalar unit instead of ~25 VALU
-// instructions each.  With m = floor(2^32 (2^l - d) / d) + 1, l = ceil(log2 d), the quotient is
-// (mulhi(n, m) + n) >> l for every n < 2^31 (mulhi(n, m) < n, so the sum cannot wrap); d == 1 is
-// m = 0, l = 0 -- no branch, so a chain of divisions does not split the scalar argument loads
-// into one wait per division.
-struct DivMagic {
-  uint32_t m;
-  int32_t l;     // 0: d == 1
-};
-inline DivMagic make_div_magic(uint32_t d) {
-  DivMagic r{0, 0};
-  if (d <= 1) return r;
-  int l = 0;
-  while ((1ull << l) < d) ++l;                                   // ceil(log2 d)
-  r.m = (uint32_t)(((((uint64_t)1 << l) - d) << 32) / d + 1);
-  r.l = l;
-  return r;
-}
-GP_DEV uint32_t div_magic(uint32_t n, DivMagic mg) {   // n < 2^31
-  return (__umulhi(n, mg.m) + n) >> mg.l;
-}
-
-
-struct AttnBranch {
-  GpBranch g;
-  int32_t nqb;          // q-blocks per (batch-segment, head)
-  int32_t n_lo;         // first segment whose dense slots meet the query window
-  int32_t nseg_w;       // segments meeting the window
-  int32_t kv_sparse;    // 0: head h at columns h*D of a k/v row; 1: at (h % hpg)*D (sparsified rows)
-  int64_t item_begin;   // first work item of this branch
-  const uint16_t* k;    // key rows: token t of batch b at row (b*L + t - kv_tok_base)
-  const uint16_t* v;
-  int64_t kv_stride;    // elements between consecutive k / v rows
-  int64_t kv_tok_base;
-  uint16_t* o;          // [B*nseg, m, H, D]
-  float* lse;           // [B*nseg, H, m]
-  int32_t kpart, kparts;   // key part kpart of kparts (<= 1: all keys; see GpAttnBranch.key_parts)
-  // varlen table entries only (one per (slide, branch); B = 1, window = the whole slide)
-  const uint16_t* q;    // the slide's first query row
-  int64_t L;            // the slide's length (CLS + tiles)
-  DivMagic d_nqb, d_nsegw, d_hpg, d_r;   // the work-item decode's divisors (scalar multiply-high)
-};
-inline void attn_branch_magic(AttnBranch& e) {
-  e.d_nqb = make_div_magic((uint32_t)e.nqb);
-  e.d_nsegw = make_div_magic((uint32_t)e.nseg_w);
-  e.d_hpg = make_div_magic((uint32_t)e.g.hpg);
-  e.d_r = make_div_magic((uint32_t)e.g.r);
-}
 
 struct AttnArgs {
   const uint16_t* q;    // query rows: token t of batch b at row (b*L + t - q_tok_base)
@@ -173,6 +124,23 @@ GP_DEV void decode_item(const AttnArgs& a, int item, WorkItem& w) {
   decode_core(a.br[bi], item - (int)a.br[bi].item_begin, a.H, a.d_H, a.L, a.win_lo, a.win_hi, w);
 }
 
+// A work-table entry by scalar loads (wave-uniform address, constant address space) instead of flat loads
+// into VGPRs
+template <class T>
+GP_DEV void load_entry_scalar(const T* src_entry, T& e) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  static_assert(sizeof(T) % 4 == 0, "");
+  uint32_t words[sizeof(T) / 4];
+  const __attribute__((address_space(4))) uint32_t* src =
+      (const __attribute__((address_space(4))) uint32_t*)(uintptr_t)src_entry;
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(T) / 4); ++i) words[i] = src[i];
+  __builtin_memcpy(&e, words, sizeof(T));
+#else
+  e = *src_entry;
+#endif
+}
+
 // Varlen (packed slides): entry = (slide, branch), items ordered by entry (heaviest first);
 // binary search on item_begin (wave-uniform), then the B = 1, whole-slide decode.
 GP_DEV void decode_item_tab(const AttnArgs& a, int item, WorkItem& w, AttnBranch& e) {
@@ -181,19 +149,8 @@ GP_DEV void decode_item_tab(const AttnArgs& a, int item, WorkItem& w, AttnBranch
     const int mid = (lo + hi + 1) >> 1;
     if ((int64_t)item >= a.tab[mid].item_begin) lo = mid; else hi = mid - 1;
   }
-  // the entry by scalar loads (uniform index, constant address space) instead of flat loads into VGPRs
   lo = __builtin_amdgcn_readfirstlane(lo);
-#if defined(__HIP_DEVICE_COMPILE__)
-  static_assert(sizeof(AttnBranch) % 4 == 0, "");
-  uint32_t words[sizeof(AttnBranch) / 4];
-  const __attribute__((address_space(4))) uint32_t* src =
-      (const __attribute__((address_space(4))) uint32_t*)(uintptr_t)(a.tab + lo);
-#pragma unroll
-  for (int i = 0; i < (int)(sizeof(AttnBranch) / 4); ++i) words[i] = src[i];
-  __builtin_memcpy(&e, words, sizeof(AttnBranch));
-#else
-  e = a.tab[lo];
-#endif
+  load_entry_scalar(a.tab + lo, e);
   w.bi = lo;
   decode_core(e, item - (int)e.item_begin, a.H, a.d_H, e.L, 0, e.L, w);
 }
@@ -209,17 +166,7 @@ GP_DEV void decode_item_list(const AttnArgs& a, int item, WorkItem& w, AttnBranc
   }
   lo = __builtin_amdgcn_readfirstlane(lo);
   AttnListEntry le;
-#if defined(__HIP_DEVICE_COMPILE__)
-  static_assert(sizeof(AttnListEntry) % 4 == 0, "");
-  uint32_t words[sizeof(AttnListEntry) / 4];
-  const __attribute__((address_space(4))) uint32_t* src =
-      (const __attribute__((address_space(4))) uint32_t*)(uintptr_t)(a.ltab + lo);
-#pragma unroll
-  for (int i = 0; i < (int)(sizeof(AttnListEntry) / 4); ++i) words[i] = src[i];
-  __builtin_memcpy(&le, words, sizeof(AttnListEntry));
-#else
-  le = a.ltab[lo];
-#endif
+  load_entry_scalar(a.ltab + lo, le);
   e = le.br;
   const GpBranch& g = e.g;
   const int local = item - (int)e.item_begin;
@@ -250,11 +197,6 @@ constexpr int kKB = 64;                      // keys per K/V tile
 // read the same K/V rows from that XCD's L2.  G is a compile-time tunable (tools/attn_lab).
 #ifndef GP_ATTN_XCDG
 #define GP_ATTN_XCDG 8
-#endif
-// GP_ATTN_WIDE_STORE: the epilogue pairs the two half-waves' 4-element groups with
-// v_permlane32_swap so every lane stores 16 contiguous bytes (3 stores instead of 6 per row)
-#ifndef GP_ATTN_WIDE_STORE
-#define GP_ATTN_WIDE_STORE 1
 #endif
 GP_DEV int64_t xcd_group(int64_t bid, int64_t nb) {
   constexpr int64_t G = GP_ATTN_XCDG, C = 8 * G;
@@ -535,27 +477,7 @@ constexpr int kFixItems = GP_ATTN_FIX_ITEMS;
 #define GP_ATTN_NW 8
 #endif
 constexpr int kNWFast = GP_ATTN_NW;
-// GP_ATTN_PRIO: the second-dispatched half of the workgroup's waves (w >= NW/2, the arbitration
-// losers of each SIMD pair) runs at s_setprio 1 for the whole kernel (MI355X_MICROARCH.md §Two waves
-// per SIMD, item 4)
-#ifndef GP_ATTN_PRIO
-#define GP_ATTN_PRIO 1
-#endif
-// the fast kernel at three workgroups per CU (GP_ATTN_FAST_WPS, round 5): no static priority -- with six
-// waves per SIMD arbitration by age alone measured 1.1-1.8 % faster (profiles/r05_occ6b_*, r05_occ6c_*)
-#ifndef GP_ATTN_PRIO_FAST
-#define GP_ATTN_PRIO_FAST 0
-#endif
 static_assert(kNWFast == 4 || kNWFast == 8 || kNWFast == 16, "GP_ATTN_NW must be 4, 8 or 16");
-#ifndef GP_ATTN_SKIP_IDLE
-#define GP_ATTN_SKIP_IDLE 1
-#endif
-// GP_ATTN_ONES_SPARSE: the V image's spare d-block carries 1.0 only in the two rows the epilogue reads
-// (d = 48 and 52) and 0 elsewhere: same outputs, fewer toggling MFMA operand bits (same-box A/B
-// 1.276 -> 1.262 ms per 70k layer, profiles/r02_s6_ab_ones.json)
-#ifndef GP_ATTN_ONES_SPARSE
-#define GP_ATTN_ONES_SPARSE 1
-#endif
 // fp16 formats of the LDS-DMA launch: GP_FMT_F16 (v fp16) runs kModeExact, the exact running-max kernel
 // (lazy rescale), no fixup pass; GP_FMT_F16_VBF16 (v bf16: the fp16 caller's fused QKV, round 5) runs the
 // bf16 product pair with fp16 S (kModeFast + kModeFix with kH).  Round 2's fp16 fast mode (p = 2^(s - m0),
@@ -575,18 +497,15 @@ static_assert(kNWFast == 4 || kNWFast == 8 || kNWFast == 16, "GP_ATTN_NW must be
 #ifndef GP_ATTN_FAST_WPS
 #define GP_ATTN_FAST_WPS 6
 #endif
-// the same for the packed (varlen, work-table) fast kernel: 6 since its table entry comes by scalar loads
+// The packed (varlen, work-table) fast kernel is sized the same since its table entry comes by scalar loads
 // (decode_item_tab); with the entry in VGPRs the 80-register budget spilled 12 and the C5 launch ran 7 % slower
 // (profiles/r05_occ6v_varlen_ab.json); with scalar loads 10.61 vs 11.00 ms per C5 launch, bit-identical
 // (profiles/r05_tab6_varlen_ab.json)
-#ifndef GP_ATTN_FAST_WPS_TAB
-#define GP_ATTN_FAST_WPS_TAB 6
-#endif
 // minimum waves per SIMD the kernel instantiation is sized for (HIP launch-bounds semantics; 2: no register
 // constraint at these sizes -- the fixup / exact / register-staged kernels, 104-138 VGPRs)
 // (the 4-wave fast kernel of under-filled launches keeps the interleaved body, no register cap)
-template <int MODE, bool kTab, int NW>
-constexpr int attn_wps() { return MODE == 0 && NW == 8 ? (kTab ? GP_ATTN_FAST_WPS_TAB : GP_ATTN_FAST_WPS) : 2; }
+template <int MODE, int NW>
+constexpr int attn_wps() { return MODE == 0 && NW == 8 ? GP_ATTN_FAST_WPS : 2; }
 // Measured lab variants of this kernel (the 16x16x32 P.V GP_ATTN_PV16, the 3-slot ring GP_ATTN_RING3) build
 // from round 3's source in git (make -C tools/attn_lab r3lab).
 
@@ -682,19 +601,15 @@ __device__ __forceinline__ void attn32_item(const AttnArgs& a, const int item_id
   const uint16_t* kbase = brr.k + (tok0 - brr.kv_tok_base) * brr.kv_stride + kcol;
   const uint16_t* vbase = brr.v + (tok0 - brr.kv_tok_base) * brr.kv_stride + kcol;
 
-  // V images: the d-columns >= D of every row (block 3 for D = 48) hold bf16 1.0
-  // (GP_ATTN_ONES_SPARSE: only d = 48 and 52, the two rows the epilogue reads; the rest 0)
+  // V images: the d-columns >= D of every row (block 3 for D = 48) hold 1.0 at d = 48 and 52, the two rows
+  // the epilogue reads, and 0 elsewhere: fewer toggling MFMA operand bits than ones throughout (same-box A/B
+  // 1.276 -> 1.262 ms per 70k layer, profiles/r02_s6_ab_ones.json)
   if constexpr (kOnes) {
     for (int idx = threadIdx.x; idx < NBUF * KT * 2; idx += NT) {   // NBUF bufs x KT rows x 2 chunks
       const int buf = idx / (2 * KT), rem = idx % (2 * KT), row = rem >> 1, half = rem & 1;
       char* const bb = smem + buf * BUF;
-#if GP_ATTN_ONES_SPARSE
       constexpr uint32_t one = kVH ? 0x3C00u : 0x3F80u;   // 1.0 in V's format
       const uint4 ones = half ? make_uint4(0u, 0u, 0u, 0u) : make_uint4(one, 0u, one, 0u);
-#else
-      constexpr uint32_t one2 = kVH ? 0x3C003C00u : 0x3F803F80u;
-      const uint4 ones = make_uint4(one2, one2, one2, one2);
-#endif
       *reinterpret_cast<uint4*>(bb + KTILE + row * VROWB + 32 * (3 ^ (row & 3)) + 16 * half) = ones;
     }
   }
@@ -826,22 +741,26 @@ __device__ __forceinline__ void attn32_item(const AttnArgs& a, const int item_id
   // prefetch -- before the first MFMA of every tile
   __builtin_amdgcn_s_waitcnt(0x0f70);
 
-  if constexpr ((attn_wps<MODE, kTab, NW>() >= 6 ? GP_ATTN_PRIO_FAST : GP_ATTN_PRIO) != 0 && NW >= 8) {
+  // the second-dispatched half of an 8 / 16-wave workgroup (w >= NW/2, the arbitration losers of each SIMD
+  // pair) runs at s_setprio 1 for the whole kernel (MI355X_MICROARCH.md §Two waves per SIMD, item 4) -- but not
+  // the fast kernel at three workgroups per CU: with six waves per SIMD arbitration by age alone measured
+  // 1.1-1.8 % faster (profiles/r05_occ6b_*, r05_occ6c_*)
+  if constexpr (attn_wps<MODE, NW>() < 6 && NW >= 8) {
     if (__builtin_amdgcn_readfirstlane((int)threadIdx.x) >= NT / 2) __builtin_amdgcn_s_setprio(1);
   }
   // one 64-key tile; SET = the tile's LDS buffer when the loop is unrolled by two (kDMA), so the
   // buffer offsets fold into the ds_read immediates
-  // GP_ATTN_SKIP_IDLE: a wave whose 32 queries all lie at or past the last needed row (the tail
-  // q-block of a segment) skips the MFMAs and the softmax -- its outputs are never stored -- and
-  // only issues its share of the K/V staging and the barriers (~2 % of the wave-tiles at 70k)
-  const bool wact = !GP_ATTN_SKIP_IDLE || __builtin_amdgcn_readfirstlane(q0 + w * 32) < (kList ? lcount : rows_needed);
+  // a wave whose 32 queries all lie at or past the last needed row (the tail q-block of a segment)
+  // skips the MFMAs and the softmax -- its outputs are never stored -- and only issues its share of
+  // the K/V staging and the barriers (~2 % of the wave-tiles at 70k)
+  const bool wact = __builtin_amdgcn_readfirstlane(q0 + w * 32) < (kList ? lcount : rows_needed);
   auto tile_step = [&](int t, auto setc) {
     constexpr int SET = decltype(setc)::value;
     if (t + 1 < t_hi) load_tile((t + 1) * KT, std::integral_constant<int, 1 - SET>());
     const int kv0 = t * KT;
     const char* Kb = kDMA ? (const char*)bufc(setc) : smem + (t & 1) * BUF;
     const char* Vb = Kb + KTILE;
-    if constexpr (attn_wps<MODE, kTab, NW>() >= 6) {
+    if constexpr (attn_wps<MODE, NW>() >= 6) {
       // the fast kernel (GP_ATTN_FAST_WPS): one 32-key sub-tile at a time -- S, exps and P.V of sub-tile u before
       // sub-tile u + 1's S -- so the body fits 80 VGPRs and three workgroups share each CU
       if (wact) {
@@ -881,7 +800,7 @@ __device__ __forceinline__ void attn32_item(const AttnArgs& a, const int item_id
           }
         }
       }
-    } else if (wact) {   // (GP_ATTN_SKIP_IDLE) waves with no needed query only stage K/V and join the barriers
+    } else if (wact) {   // waves with no needed query only stage K/V and join the barriers
       // ---- S^T for two 32-key sub-tiles.  kPre (q pre-multiplied by scale*log2 e): the
       // accumulator starts at -m_run, so it already holds log2-domain scores minus the max.
       f32x16 sacc[2];
@@ -1084,10 +1003,11 @@ __device__ __forceinline__ void attn32_item(const AttnArgs& a, const int item_id
   }
   const float inv = empty ? 0.f : so / l;
   const int i = kList ? irow : q0 + w * 32 + l32;
-  if constexpr (GP_ATTN_WIDE_STORE != 0) {
+  {
     // lane (q, h) holds d = 8k + 4h .. +3 for the D/8 groups k.  For each pair of groups (k, k+1)
     // one permlane32_swap per dword gives lanes 0-31 d = 8k .. 8k+7 and lanes 32-63 d = 8k+8 .. 8k+15
-    // (T21): one 16-byte store per pair.  The swap needs EXEC full: it runs before the row check.
+    // (T21): one 16-byte store per pair (3 stores instead of 6 per row).  The swap needs EXEC full: it runs
+    // before the row check.
     uint2 pk[D / 8];
 #pragma unroll
     for (int k = 0; k < D / 8; ++k) {
@@ -1108,19 +1028,6 @@ __device__ __forceinline__ void attn32_item(const AttnArgs& a, const int item_id
       for (int k = 0; k < D / 8; k += 2)
         *reinterpret_cast<uint4*>(orow + 8 * k) = make_uint4(pk[k].x, pk[k].y, pk[k + 1].x, pk[k + 1].y);
     }
-  } else if (i < rows_needed && fixrow) {
-    uint16_t* orow = brr.o + (((int64_t)bn * g.m + i) * a.H + hh) * (int64_t)D;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        const int d0 = 32 * mt + 8 * rg + 4 * h;
-        if (d0 < D) {
-          float vv[4] = {oacc[mt][4 * rg] * inv, oacc[mt][4 * rg + 1] * inv, oacc[mt][4 * rg + 2] * inv,
-                         oacc[mt][4 * rg + 3] * inv};
-          store_e<kH, 4>(orow + d0, vv);
-        }
-      }
   }
   if (i < rows_needed && fixrow) {
     float lse = empty ? -INFINITY : (mr + __builtin_amdgcn_logf(l)) * 0.69314718055994530942f;
@@ -1139,7 +1046,7 @@ __device__ __forceinline__ void attn32_item(const AttnArgs& a, const int item_id
 // (kList: the fixup pass is one block per item -- a list launch holds few items)
 template <int D, bool kPre, int MODE, bool kTab = false, int NW = 4, bool kH = false, bool kParts = false,
           bool kList = false>
-__global__ __launch_bounds__(NW * 64, (attn_wps<MODE, kTab, NW>())) void dilated_attn32_kernel(const AttnArgs a) {
+__global__ __launch_bounds__(NW * 64, (attn_wps<MODE, NW>())) void dilated_attn32_kernel(const AttnArgs a) {
   if constexpr (kList) {
     attn32_item<D, kPre, MODE, kTab, NW, kH, kParts, true>(
         a, MODE == kModeFix ? (int)blockIdx.x : (int)xcd_group(blockIdx.x, gridDim.x));
@@ -1183,689 +1090,41 @@ __global__ __launch_bounds__(NW * 64, (attn_wps<MODE, kTab, NW>())) void dilated
     attn32_item<D, kPre, MODE, kTab, NW, kH, kParts>(a, (int)xcd_group(blockIdx.x, gridDim.x));
   }
 }
-// ---------------------------------------------------------------------------------------
-struct MergeBranch {
-  GpBranch g;
-  const uint16_t* o;
-  const float* lse;
-  DivMagic dg, dr;   // division by g.g and by g.r
-};
-inline void merge_branch_magic(MergeBranch& m) {
-  m.dg = make_div_magic((uint32_t)m.g.g);
-  m.dr = make_div_magic((uint32_t)m.g.r);
-}
 
-struct MergeArgs {
-  int64_t B, L;
-  int64_t tok_lo, ntok;   // window of tokens [tok_lo, tok_lo + ntok) of every batch; out row = b*ntok + t
-  int32_t H, D, E, nbranch;
-  MergeBranch br[GP_MAX_BRANCHES];
-  const float* ln_w;
-  const float* ln_b;
-  float eps;
-  uint16_t* out;
-  // varlen (packed slides): slide i owns packed tokens [tok_off[i], tok_off[i+1]); its branch b
-  // geometry and o/lse regions are mtab[i * nbranch + b]
-  const MergeBranch* mtab;
-  const int64_t* tok_off;
-  int32_t nslide;
-  DivMagic dnt;        // division by ntok (the batch index of a row)
-  // token list (branch_merge_v3_kernel kList, gp_branch_merge_ln_rows): out row b*ntok + k is token tok_list[k]
-  const int32_t* tok_list;
-};
-
-// One wave per run of kTPW consecutive tokens; lane l owns the EPL = E/64 contiguous elements
-// [l*EPL, (l+1)*EPL) of head l*EPL/D (EPL divides D).  The sparse_to_dense position of the
-// token in every branch -- segment n, dense slot t = p mod g, sparse row i = t / r, phase
-// jj = t mod r -- is wave-uniform: divided out once per run, then stepped token by token.  The
-// lanes a branch covers for phase jj are the contiguous range [jj*LPH, (jj+1)*LPH), LPH = lanes
-// per head group.  Math per token is that of dilated_attention.py:100-131 (fp32 weights,
-// branch-order accumulation) followed by inner_attn_ln.
-constexpr int kTPW = 1;
-
-// NBR < GP_MAX_BRANCHES: the launch guarantees a.nbranch == NBR, so the branch loops have a
-// compile-time trip count (the 5-branch schedule of every registered arch: 3 dead branches of
-// position stepping, address math and exp fewer per token)
-template <int EPL, int D, bool kTab = false, int NBR = GP_MAX_BRANCHES, bool kH = false>
-__global__ __launch_bounds__(256) void branch_merge_kernel(const MergeArgs a) {
-  const int nbr = NBR < GP_MAX_BRANCHES ? NBR : a.nbranch;
-  const int lane = threadIdx.x & 63;
-  const int run = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6));
-  const int total = (int)(a.B * a.ntok);
-  const int r0 = run * kTPW;
-  if (r0 >= total) return;
-  // kTab: the token's slide (binary search, wave-uniform) and that slide's branch entries
-  MergeBranch tb[kTab ? GP_MAX_BRANCHES : 1];
-  int64_t slide_tok0 = 0;
-  if constexpr (kTab) {
-    int lo = 0, hi = a.nslide - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if ((int64_t)r0 >= a.tok_off[mid]) lo = mid; else hi = mid - 1;
-    }
-    slide_tok0 = a.tok_off[lo];
-#pragma unroll
-    for (int b = 0; b < NBR; ++b)
-      if (b < nbr) tb[b] = a.mtab[lo * a.nbranch + b];
-  }
-  const int nt = (int)a.ntok;
-  const int E = 64 * EPL;
-  const int col0 = lane * EPL;
-  int pn[GP_MAX_BRANCHES], pt[GP_MAX_BRANCHES], pi[GP_MAX_BRANCHES], pj[GP_MAX_BRANCHES];
-  int bidx = 0, p = 0;
-  for (int k = 0; k < kTPW; ++k) {
-    const int row = r0 + k;
-    if (row >= total) break;
-    if (k == 0 || p + 1 >= (int)a.tok_lo + nt) {   // (re)derive positions: run start / next batch
-      if constexpr (kTab) {
-        bidx = 0;
-        p = (int)(row - slide_tok0);
-      } else {
-        bidx = (int)div_magic((uint32_t)row, a.dnt);
-        p = (int)a.tok_lo + (row - bidx * nt);
-      }
-#pragma unroll
-      for (int b = 0; b < NBR; ++b)
-        if (b < nbr) {
-          const MergeBranch& mb = kTab ? tb[b] : a.br[b];
-          pn[b] = (int)div_magic((uint32_t)p, mb.dg);
-          pt[b] = p - pn[b] * mb.g.g;
-          pi[b] = (int)div_magic((uint32_t)pt[b], mb.dr);
-          pj[b] = pt[b] - pi[b] * mb.g.r;
-        }
-    } else {
-      ++p;
-#pragma unroll
-      for (int b = 0; b < NBR; ++b)
-        if (b < nbr) {
-          const GpBranch& g = (kTab ? tb[b] : a.br[b]).g;
-          if (++pt[b] == g.g) { pt[b] = 0; ++pn[b]; pi[b] = 0; pj[b] = 0; }
-          else if (++pj[b] == g.r) { pj[b] = 0; ++pi[b]; }
-        }
-    }
-    // Every branch's loads are issued before any wait, with no exec-mask region around them: a
-    // lane outside the branch's head group reads the group's first lane's o / lse (the same
-    // cache lines, no extra traffic) and its weight is forced to zero below.  (Loads guarded by
-    // `if (covered)` compiled to one wait per branch -- five serial memory latencies per token.)
-    float lse[GP_MAX_BRANCHES];
-    bool cov[GP_MAX_BRANCHES];
-    uint2 ob[GP_MAX_BRANCHES][EPL / 4];
-#pragma unroll
-    for (int b = 0; b < NBR; ++b) {
-      lse[b] = -1e8f;
-      cov[b] = false;
-      if (b < nbr) {
-        const MergeBranch& mb = kTab ? tb[b] : a.br[b];
-        const int lph = mb.g.hpg * (D / EPL);     // lanes per head group
-        const int l0 = pj[b] * lph;
-        cov[b] = lane >= l0 && lane < l0 + lph;
-        const int ln = cov[b] ? lane : l0;
-        const int64_t rb = (int64_t)(bidx * mb.g.nseg + pn[b]);
-        lse[b] = mb.lse[(rb * a.H + ln * EPL / D) * mb.g.m + pi[b]];
-        const uint2* src = reinterpret_cast<const uint2*>(mb.o + (rb * mb.g.m + pi[b]) * E + ln * EPL);
-#pragma unroll
-        for (int q = 0; q < EPL / 4; ++q) ob[b][q] = src[q];
-      }
-    }
-    float wv[EPL], bv[EPL];
-    if (a.ln_w != nullptr) {   // LN affine via L1, in flight with the o rows (-5 % vs loading after the sums)
-      load_f32<EPL>(a.ln_w + col0, wv);
-      load_f32<EPL>(a.ln_b + col0, bv);
-    }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int b = 0; b < NBR; ++b)
-      if (b < nbr) {
-        if (!cov[b] || lse[b] == 0.f) lse[b] = -1e8f;   // dilated_attention.py:46
-        mx = fmaxf(mx, lse[b]);
-      }
-    float wsum = 0.f;
-#pragma unroll
-    for (int b = 0; b < NBR; ++b)
-      if (b < nbr) {
-        // v_exp_f32 / v_rcp_f32 (1 ulp) instead of the libm expf and the IEEE division sequence: the
-        // weights are fp32 (the reference rounds them to the activation dtype, dilated_attention.py:128)
-        lse[b] = fast_exp2((lse[b] - mx) * 1.44269504088896340736f);
-        wsum += lse[b];
-      }
-    const float inv = __builtin_amdgcn_rcpf(wsum);
-    float acc[EPL];
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) acc[e] = 0.f;
-#pragma unroll
-    for (int b = 0; b < NBR; ++b) {
-      if (b < nbr) {
-        const float wb = cov[b] ? lse[b] * inv : 0.f;   // + 0 * finite leaves acc unchanged
-#pragma unroll
-        for (int q = 0; q < EPL / 4; ++q) {
-          // explicit fma: every instantiation (and the varlen path) rounds identically
-          acc[4 * q + 0] = __builtin_fmaf(e2f<kH>(ob[b][q].x), wb, acc[4 * q + 0]);
-          acc[4 * q + 1] = __builtin_fmaf(e2f_hi<kH>(ob[b][q].x), wb, acc[4 * q + 1]);
-          acc[4 * q + 2] = __builtin_fmaf(e2f<kH>(ob[b][q].y), wb, acc[4 * q + 2]);
-          acc[4 * q + 3] = __builtin_fmaf(e2f_hi<kH>(ob[b][q].y), wb, acc[4 * q + 3]);
-        }
-      }
-    }
-    if (a.ln_w != nullptr) wave_layernorm_regs<EPL>(acc, E, wv, bv, a.eps);
-    store_e<kH, EPL>(a.out + (int64_t)row * E + col0, acc);
+// The product pair on one stream: the no-max kernel on one block per item, then the fixup pass (exits at once
+// unless a row was flagged) on kFixItems items per block -- one item per block for a query-list launch.
+template <bool kTab, int NW, bool kH, bool kParts = false, bool kList = false>
+void launch_fast_fix(const AttnArgs& a, hipStream_t s) {
+  const int64_t items = a.total_items;
+  dilated_attn32_kernel<48, true, kModeFast, kTab, NW, kH, kParts, kList><<<(unsigned)items, 64 * NW, 0, s>>>(a);
+  if constexpr (GP_ATTN_NOFIX == 0) {
+    const unsigned fix_blocks = (unsigned)(kList ? items : (items + kFixItems - 1) / kFixItems);
+    dilated_attn32_kernel<48, true, kModeFix, kTab, NW, kH, kParts, kList><<<fix_blocks, 64 * NW, 0, s>>>(a);
   }
 }
 
-// ---------------------------------------------------------------------------------------
-// Merge for E = 768, D = 48 (H = 16: every registered 768-wide arch, the product path), one token per
-// wave as branch_merge_kernel, with fewer vector instructions per token (that kernel issues ~380 VALU
-// per token-wave, ~70 of them 64-bit per-lane address arithmetic, and 12 dependent ds_bpermute for the
-// LN sums):
-//  * a lane owns two column chunks: 8 columns (one 16-byte access) and 4 columns (one 8-byte access)
-//    instead of three 8-byte accesses of 12 contiguous columns.  kMap 1 ("x8", the default): [8l, 8l + 8)
-//    of head l / 6 and [512 + 4l, 516 + 4l) of head (128 + l) / 12, so each wave-instruction covers one
-//    contiguous span (two heads per lane: twice the softmax VALU, yet measured faster: the kernel is bound
-//    by memory requests, not issue); kMap 0: both chunks in head l / 4 (lane k of a head: columns 8k..
-//    and 32 + 4k.. of the head, one softmax per lane);
-//  * loads address a wave-uniform row base plus a 32-bit lane offset (no per-lane 64-bit math);
-//  * the LN row sums are xor-butterflies (DPP quad_perm / row_half_mirror / row_ror:8, then
-//    v_permlane16/32_swap): the same sum in every lane, no LDS round trips.
-// Per (token, head) the branch weights and the fp32 accumulation are branch_merge_kernel's bit for bit
-// (dilated_attention.py:100-131).
-#ifndef GP_MERGE_MAP
-#define GP_MERGE_MAP 1
-#endif
-// waves (tokens) per block of the v2 merge: consecutive tokens of one block share their lse / o lines in L1
-#ifndef GP_MERGE_WPB
-#define GP_MERGE_WPB 4
-#endif
-
-// A 32-bit lane offset the compiler may not re-associate with constants: keeps a uniform-base + lane-offset
-// load in its SGPR-base (saddr) form instead of a per-lane 64-bit address.
-GP_DEV uint32_t opaque_u32(uint32_t x) {
-  __asm__("" : "+v"(x));
-  return x;
+// The exact kernels with register-staged K/V (any k / v layout, q pre-scaled or not): 4 waves, one block per item
+template <bool kH>
+void launch_attn_gen(const AttnArgs& a, int D, bool pre, hipStream_t s) {
+  const unsigned items = (unsigned)a.total_items;
+  if (D == 96) dilated_attn_kernel<96, kH><<<items, 256, 0, s>>>(a);
+  else if (D == 48 && pre) dilated_attn32_kernel<48, true, kModeGen, false, 4, kH><<<items, 256, 0, s>>>(a);
+  else if (D == 48) dilated_attn32_kernel<48, false, kModeGen, false, 4, kH><<<items, 256, 0, s>>>(a);
+  else if (pre) dilated_attn32_kernel<64, true, kModeGen, false, 4, kH><<<items, 256, 0, s>>>(a);
+  else dilated_attn32_kernel<64, false, kModeGen, false, 4, kH><<<items, 256, 0, s>>>(a);
 }
 
-GP_DEV float wave_sum_xor(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, false));   // quad_perm 1,0,3,2
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xf, 0xf, false));   // quad_perm 2,3,0,1
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, false));  // row_half_mirror
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, false));  // row_ror:8
-  const auto s16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = __uint_as_float(s16[0]) + __uint_as_float(s16[1]);
-  const auto s32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(s32[0]) + __uint_as_float(s32[1]);
+// order[]: the branches by sparse rows per segment (keys per work item), descending, so the longest items
+// start first; equal branches keep their input order (insertion sort)
+void order_by_rows_desc(const GpBranch* geo, int nbranch, int* order) {
+  for (int b = 0; b < nbranch; ++b) order[b] = b;
+  for (int x = 1; x < nbranch; ++x)
+    for (int y = x; y > 0 && geo[order[y]].m > geo[order[y - 1]].m; --y) std::swap(order[y], order[y - 1]);
 }
-
-template <int NBR, bool kTab, bool kH, int kMap = GP_MERGE_MAP>
-__global__ __launch_bounds__(64 * GP_MERGE_WPB) void branch_merge_v2_kernel(const MergeArgs a) {
-  // no implicit contraction: the compiler fused v - s * (1/E) into one fma in some instantiations only, so the
-  // packed (varlen) and single-slide merges differed in the last bit; every fma below is explicit
-#pragma clang fp contract(off)
-  constexpr int E = 768, H = 16, D = 48;
-  constexpr bool k1h = kMap == 0;          // one head per lane
-  const int nbr = NBR < GP_MAX_BRANCHES ? NBR : a.nbranch;
-  const int lane = threadIdx.x & 63;
-  const int row = __builtin_amdgcn_readfirstlane((int)blockIdx.x * GP_MERGE_WPB + (int)(threadIdx.x >> 6));
-  const int total = (int)(a.B * a.ntok);
-  if (row >= total) return;
-  // the lane's chunks: columns c0 .. c0 + 7 (head h0) and c1 .. c1 + 3 (head h1)
-  const int kq = lane & 3;
-  const int h0 = k1h ? lane >> 2 : lane / 6;
-  const int h1 = k1h ? h0 : (128 + lane) / 12;
-  const int c0 = k1h ? D * h0 + 8 * kq : 8 * lane;
-  const int c1 = k1h ? D * h0 + 32 + 4 * kq : 512 + 4 * lane;
-  // LN affine (L1-resident): issued with the branch loads; nothing is read without an LN (a null ln_w)
-  const bool ln = a.ln_w != nullptr;
-  float w0[8] = {}, w1[4] = {}, b0[8] = {}, b1[4] = {};
-  if (ln) {
-    load_f32<8>(a.ln_w + c0, w0);
-    load_f32<4>(a.ln_w + c1, w1);
-    load_f32<8>(a.ln_b + c0, b0);
-    load_f32<4>(a.ln_b + c1, b1);
-  }
-  int bidx = 0, p;
-  MergeBranch tb[kTab ? GP_MAX_BRANCHES : 1];
-  if constexpr (kTab) {
-    int lo = 0, hi = a.nslide - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if ((int64_t)row >= a.tok_off[mid]) lo = mid; else hi = mid - 1;
-    }
-    p = (int)(row - a.tok_off[lo]);
-#pragma unroll
-    for (int b = 0; b < NBR; ++b)
-      if (b < nbr) tb[b] = a.mtab[lo * a.nbranch + b];
-  } else {
-    bidx = (int)div_magic((uint32_t)row, a.dnt);
-    p = (int)a.tok_lo + (row - bidx * (int)a.ntok);
-  }
-  // every branch's loads before any wait; a lane outside the branch's head group reads the group's
-  // first head (same cache lines as the covered lanes) and gets weight 0
-  uint4 o0[NBR];
-  uint2 o1[NBR];
-  float l0[NBR], l1[NBR];
-  bool cv0[NBR], cv1[NBR];
-#pragma unroll
-  for (int b = 0; b < NBR; ++b) {
-    cv0[b] = cv1[b] = false;
-    l0[b] = l1[b] = -1e8f;
-    o0[b] = make_uint4(0, 0, 0, 0);
-    o1[b] = make_uint2(0, 0);
-    if (b < nbr) {
-      const MergeBranch& mb = kTab ? tb[b] : a.br[b];
-      const int pn = (int)div_magic((uint32_t)p, mb.dg);
-      const int pt = p - pn * mb.g.g;
-      const int pi = (int)div_magic((uint32_t)pt, mb.dr);
-      const int pj = pt - pi * mb.g.r;
-      const int hpg = mb.g.hpg;
-      const int hf = pj * hpg;                                 // the covered group's first head
-      // 32-bit byte offsets: the launch checks every branch's o / lse buffer is below 4 GiB
-      const uint32_t rb = (uint32_t)(bidx * mb.g.nseg + pn);
-      const char* orow = reinterpret_cast<const char*>(mb.o) + (rb * (uint32_t)mb.g.m + (uint32_t)pi) * (uint32_t)(E * 2);
-      const char* lrow = reinterpret_cast<const char*>(mb.lse) + (rb * (uint32_t)(H * mb.g.m) + (uint32_t)pi) * 4u;
-      const uint32_t m4 = (uint32_t)mb.g.m * 4u;
-      cv0[b] = (unsigned)(h0 - hf) < (unsigned)hpg;
-      const int s0 = cv0[b] ? h0 : hf;
-      // (m < 2^22 for any segment of the schedule: 24-bit multiplies)
-      l0[b] = *reinterpret_cast<const float*>(lrow + opaque_u32(__umul24((uint32_t)s0, m4)));
-      if constexpr (k1h) {
-        cv1[b] = cv0[b];
-        const uint32_t off0 = __umul24((uint32_t)s0, 2u * D) + 16u * kq;   // head s0, lane kq's columns
-        const uint32_t off1 = off0 + (uint32_t)(64 - 8 * kq);
-        o0[b] = *reinterpret_cast<const uint4*>(orow + opaque_u32(off0));
-        o1[b] = *reinterpret_cast<const uint2*>(orow + opaque_u32(off1));
-      } else {
-        cv1[b] = (unsigned)(h1 - hf) < (unsigned)hpg;
-        l1[b] = *reinterpret_cast<const float*>(lrow + opaque_u32(__umul24((uint32_t)(cv1[b] ? h1 : hf), m4)));
-        o0[b] = *reinterpret_cast<const uint4*>(orow + opaque_u32(cv0[b] ? 2 * c0 : 2 * D * hf));
-        o1[b] = *reinterpret_cast<const uint2*>(orow + opaque_u32(cv1[b] ? 2 * c1 : 2 * D * hf));
-      }
-    }
-  }
-  // per-head softmax over the branches (k1h: one head per lane)
-  float mx0 = -INFINITY, mx1 = -INFINITY;
-#pragma unroll
-  for (int b = 0; b < NBR; ++b)
-    if (b < nbr) {
-      if (!cv0[b] || l0[b] == 0.f) l0[b] = -1e8f;   // dilated_attention.py:46
-      mx0 = fmaxf(mx0, l0[b]);
-      if constexpr (!k1h) {
-        if (!cv1[b] || l1[b] == 0.f) l1[b] = -1e8f;
-        mx1 = fmaxf(mx1, l1[b]);
-      }
-    }
-  float ws0 = 0.f, ws1 = 0.f;
-#pragma unroll
-  for (int b = 0; b < NBR; ++b)
-    if (b < nbr) {
-      l0[b] = fast_exp2((l0[b] - mx0) * 1.44269504088896340736f);
-      ws0 += l0[b];
-      if constexpr (!k1h) {
-        l1[b] = fast_exp2((l1[b] - mx1) * 1.44269504088896340736f);
-        ws1 += l1[b];
-      }
-    }
-  const float inv0 = __builtin_amdgcn_rcpf(ws0), inv1 = k1h ? inv0 : __builtin_amdgcn_rcpf(ws1);
-  float v[12];
-#pragma unroll
-  for (int e = 0; e < 12; ++e) v[e] = 0.f;
-#pragma unroll
-  for (int b = 0; b < NBR; ++b)
-    if (b < nbr) {
-      const float wb0 = cv0[b] ? l0[b] * inv0 : 0.f;   // + 0 * finite leaves v unchanged
-      const float wb1 = k1h ? wb0 : (cv1[b] ? l1[b] * inv1 : 0.f);
-      const uint32_t u0[4] = {o0[b].x, o0[b].y, o0[b].z, o0[b].w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        v[2 * k] = __builtin_fmaf(e2f<kH>(u0[k]), wb0, v[2 * k]);
-        v[2 * k + 1] = __builtin_fmaf(e2f_hi<kH>(u0[k]), wb0, v[2 * k + 1]);
-      }
-      v[8] = __builtin_fmaf(e2f<kH>(o1[b].x), wb1, v[8]);
-      v[9] = __builtin_fmaf(e2f_hi<kH>(o1[b].x), wb1, v[9]);
-      v[10] = __builtin_fmaf(e2f<kH>(o1[b].y), wb1, v[10]);
-      v[11] = __builtin_fmaf(e2f_hi<kH>(o1[b].y), wb1, v[11]);
-    }
-  if (ln) {
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < 12; ++e) s += v[e];
-    const float mean = wave_sum_xor(s) * (1.0f / E);
-    // explicit fmas: every instantiation (the varlen one included) rounds the LN identically
-    float q = 0.f;
-#pragma unroll
-    for (int e = 0; e < 12; ++e) {
-      const float d = v[e] - mean;
-      q = __builtin_fmaf(d, d, q);
-    }
-    const float rstd = rsqrtf(__builtin_fmaf(wave_sum_xor(q), 1.0f / E, a.eps));
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = __builtin_fmaf((v[e] - mean) * rstd, w0[e], b0[e]);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[8 + e] = __builtin_fmaf((v[8 + e] - mean) * rstd, w1[e], b1[e]);
-  }
-  char* orow = reinterpret_cast<char*>(a.out) + (int64_t)row * (E * 2);
-  *reinterpret_cast<uint4*>(orow + 2 * c0) =
-      make_uint4(pack2e<kH>(v[0], v[1]), pack2e<kH>(v[2], v[3]), pack2e<kH>(v[4], v[5]), pack2e<kH>(v[6], v[7]));
-  *reinterpret_cast<uint2*>(orow + 2 * c1) = make_uint2(pack2e<kH>(v[8], v[9]), pack2e<kH>(v[10], v[11]));
-}
-
-// GP_MERGE_V3 (round 6, product 1): the v2 merge with the LSEs staged per block of up to kV3Tok consecutive tokens.  The
-// [B * nseg, H, m] lse layout puts one token's covered heads in 16 / r different cache lines, and the v2 kernel's
-// one-token waves fetch them token by token (~16 of its ~42 L2 read requests per token, at the per-CU cap of
-// outstanding requests, §3.5).  Here the block's four waves first load every lse its 64 tokens need -- lane t =
-// token t, so one wave-instruction reads up to 64 consecutive rows of a head -- into LDS, then each wave merges
-// a quarter of the tokens (t = wave + 4k) exactly as branch_merge_v2_kernel does, reading the weights' LSEs from
-// LDS.  Same arithmetic per token, so the same bits (the varlen merge too, GP_MERGE_V3_TAB).  Same-process A/B
-// (profiles/r06_mv3e_merge_ab_*): 70k 73.5 vs 84.2 us, 256k 238 vs 284 us per launch, bit-identical; up to 64
-// tokens per block 82.5 / 246 us, 16: 82.0 / 272 us.
-#ifndef GP_MERGE_V3
-#define GP_MERGE_V3 1
-#endif
-// GP_MERGE_V3_TAB (product 1): the packed-slide (varlen) merge on the v3 kernel too, when every slide holds at least a
-// block's tokens: C5 batch (675,619 tokens) 0.625 vs 0.868 ms per launch, bit-identical (profiles/r06_mv3tab2_*)
-#ifndef GP_MERGE_V3_TAB
-#define GP_MERGE_V3_TAB 1
-#endif
-#ifndef GP_MERGE_V3_TOK
-#define GP_MERGE_V3_TOK 32
-#endif
-constexpr int kV3Tok = GP_MERGE_V3_TOK;    // most tokens per block (4 waves, up to kV3Tok / 4 tokens each); <= 64
-
-// entry k of the token list, held inside [0, L): a bad list cannot send a load outside the branch buffers
-GP_DEV int list_token(const MergeArgs& a, int k) {
-  const int p = a.tok_list[k];
-  return p < 0 ? 0 : (p < (int)a.L ? p : (int)a.L - 1);
-}
-
-// A MergeBranch table entry by scalar loads (uniform index, constant address space): the entries then live in
-// SGPRs even when the load follows the kernel's global stores (the compiler's uniform-load analysis would
-// otherwise fall back to per-lane loads into VGPRs)
-GP_DEV MergeBranch merge_entry_scalar(const MergeBranch* tab, int idx) {
-  MergeBranch e;
-#if defined(__HIP_DEVICE_COMPILE__)
-  static_assert(sizeof(MergeBranch) % 4 == 0, "");
-  uint32_t words[sizeof(MergeBranch) / 4];
-  const __attribute__((address_space(4))) uint32_t* src =
-      (const __attribute__((address_space(4))) uint32_t*)(uintptr_t)(tab + __builtin_amdgcn_readfirstlane(idx));
-#pragma unroll
-  for (int i = 0; i < (int)(sizeof(MergeBranch) / 4); ++i) words[i] = src[i];
-  __builtin_memcpy(&e, words, sizeof(MergeBranch));
-#else
-  e = tab[idx];
-#endif
-  return e;
-}
-
-// kList (gp_branch_merge_ln_rows): output row b*ntok + k merges token tok_list[k] of batch b instead of token
-// tok_lo + k -- the only difference, so a listed token's row holds the bits the full merge writes for it.
-template <int NBR, bool kH, bool kTab = false, bool kList = false>
-__global__ __launch_bounds__(256) void branch_merge_v3_kernel(const MergeArgs a, const int tpb) {
-#pragma clang fp contract(off)
-  static_assert(!(kTab && kList), "token list: [B, L] batches only");
-  constexpr int E = 768, H = 16, D = 48;
-  constexpr int LS = NBR * 16 + 1;           // LDS floats per token (16 per branch entry; +1: bank spread)
-  __shared__ float lse_s[kV3Tok * LS];
-  const int nbr = NBR < GP_MAX_BRANCHES ? NBR : a.nbranch;
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  const int total = (int)(a.B * a.ntok);
-  const int row0 = (int)blockIdx.x * tpb;    // tpb <= kV3Tok tokens of this block (the launch balances them)
-  // kTab (packed slides): the slide of the block's first token (wave-uniform binary search); a block of at most
-  // kV3Tok tokens meets at most two slides (every slide holds more tokens than that, checked by the launch)
-  int slide0 = 0;
-  if constexpr (kTab) {
-    int lo = 0, hi = a.nslide - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if ((int64_t)row0 >= a.tok_off[mid]) lo = mid; else hi = mid - 1;
-    }
-    slide0 = __builtin_amdgcn_readfirstlane(lo);
-  }
-  // ---- stage: lane t loads, for token row0 + t, the covered heads' lse of every branch (wave w: heads h' = w mod 4)
-  if constexpr (!kTab) {
-    if (lane < tpb) {
-      const int tl = lane;
-      const int row = row0 + tl;
-      const bool live = row < total;
-      const int rr = live ? row : total - 1;
-      const int bidx = (int)div_magic((uint32_t)rr, a.dnt);
-      const int p = kList ? list_token(a, rr - bidx * (int)a.ntok) : (int)a.tok_lo + (rr - bidx * (int)a.ntok);
-#pragma unroll
-      for (int b = 0; b < NBR; ++b) {
-        if (b < nbr) {
-          const MergeBranch& mb = a.br[b];
-          const int pn = (int)div_magic((uint32_t)p, mb.dg);
-          const int pt = p - pn * mb.g.g;
-          const int pi = (int)div_magic((uint32_t)pt, mb.dr);
-          const int pj = pt - pi * mb.g.r;
-          const int hpg = mb.g.hpg;
-          const uint32_t rb = (uint32_t)(bidx * mb.g.nseg + pn);
-          const float* lrow = mb.lse + (size_t)rb * (uint32_t)(H * mb.g.m) + (uint32_t)pi;
-          for (int hq = wv; hq < hpg; hq += 4) {
-            const float v = lrow[(size_t)(uint32_t)(pj * hpg + hq) * (uint32_t)mb.g.m];
-            lse_s[tl * LS + b * 16 + hq] = v;
-          }
-        }
-      }
-    }
-  } else {
-#pragma unroll
-    for (int pass = 0; pass < (kTab ? 2 : 1); ++pass) {
-      int s_lo = 0, s_hi = total;
-      MergeBranch tb[kTab ? NBR : 1];
-      if constexpr (kTab) {
-        const int sl = slide0 + pass;
-        if (sl >= a.nslide) break;
-        s_lo = (int)a.tok_off[sl];
-        s_hi = (int)a.tok_off[sl + 1];
-#pragma unroll
-        for (int b = 0; b < NBR; ++b)
-          if (b < nbr) tb[b] = a.mtab[sl * a.nbranch + b];
-      }
-      const int tl = lane;
-      const int row = row0 + tl;
-      if (tl < tpb && row < total && row >= s_lo && row < s_hi) {
-        int bidx = 0, p;
-        if constexpr (kTab) {
-          p = row - s_lo;
-        } else {
-          bidx = (int)div_magic((uint32_t)row, a.dnt);
-          p = (int)a.tok_lo + (row - bidx * (int)a.ntok);
-        }
-#pragma unroll
-        for (int b = 0; b < NBR; ++b) {
-          if (b < nbr) {
-            const MergeBranch& mb = kTab ? tb[b] : a.br[b];
-            const int pn = (int)div_magic((uint32_t)p, mb.dg);
-            const int pt = p - pn * mb.g.g;
-            const int pi = (int)div_magic((uint32_t)pt, mb.dr);
-            const int pj = pt - pi * mb.g.r;
-            const int hpg = mb.g.hpg;
-            const uint32_t rb = (uint32_t)(bidx * mb.g.nseg + pn);
-            const float* lrow = mb.lse + (size_t)rb * (uint32_t)(H * mb.g.m) + (uint32_t)pi;
-            for (int hq = wv; hq < hpg; hq += 4) {
-              const float v = lrow[(size_t)(uint32_t)(pj * hpg + hq) * (uint32_t)mb.g.m];
-              lse_s[tl * LS + b * 16 + hq] = v;
-            }
-          }
-        }
-      }
-    }
-  }
-  __syncthreads();
-  // ---- merge: wave wv takes tokens wv, wv + 4, ..., as branch_merge_v2_kernel (kMap 1, "x8") does one token
-  const int kq = lane & 3;
-  (void)kq;
-  const int h0 = lane / 6, h1 = (128 + lane) / 12;
-  const int c0 = 8 * lane, c1 = 512 + 4 * lane;
-  const bool ln = a.ln_w != nullptr;
-  float w0[8] = {}, w1[4] = {}, b0[8] = {}, b1[4] = {};
-  if (ln) {                                  // (without an LN nothing is read: the output may be a small buffer)
-    load_f32<8>(a.ln_w + c0, w0);
-    load_f32<4>(a.ln_w + c1, w1);
-    load_f32<8>(a.ln_b + c0, b0);
-    load_f32<4>(a.ln_b + c1, b1);
-  }
-  // kTab: the first slide's entries, loaded once for the wave's tokens (its tokens ascend, so a crossing into
-  // the next slide happens at most once)
-  MergeBranch tb[kTab ? NBR : 1];
-  int t_sl = 0, t_base = 0, t_bnd = INT_MAX;
-  if constexpr (kTab) {
-    t_sl = slide0;
-    t_base = (int)a.tok_off[slide0];
-    t_bnd = slide0 + 1 < a.nslide ? (int)a.tok_off[slide0 + 1] : INT_MAX;
-#pragma unroll
-    for (int b = 0; b < NBR; ++b)
-      if (b < nbr) tb[b] = merge_entry_scalar(a.mtab, slide0 * a.nbranch + b);
-  }
-  for (int k = 0; k < kV3Tok / 4; ++k) {
-    const int t = wv + 4 * k;
-    const int row = row0 + t;
-    if (t >= tpb || row >= total) break;
-    int bidx = 0, p;
-    if constexpr (kTab) {
-      if (row >= t_bnd) {                    // this wave's tokens crossed into the next slide (rare): switch tables
-        t_sl += 1;
-        t_base = t_bnd;
-        t_bnd = t_sl + 1 < a.nslide ? (int)a.tok_off[t_sl + 1] : INT_MAX;
-#pragma unroll
-        for (int b = 0; b < NBR; ++b)
-          if (b < nbr) tb[b] = merge_entry_scalar(a.mtab, t_sl * a.nbranch + b);
-      }
-      p = row - t_base;
-    } else {
-      bidx = (int)div_magic((uint32_t)row, a.dnt);
-      p = kList ? list_token(a, row - bidx * (int)a.ntok) : (int)a.tok_lo + (row - bidx * (int)a.ntok);
-    }
-    uint4 o0[NBR];
-    uint2 o1[NBR];
-    float l0[NBR], l1[NBR];
-    bool cv0[NBR], cv1[NBR];
-#pragma unroll
-    for (int b = 0; b < NBR; ++b) {
-      cv0[b] = cv1[b] = false;
-      l0[b] = l1[b] = -1e8f;
-      o0[b] = make_uint4(0, 0, 0, 0);
-      o1[b] = make_uint2(0, 0);
-      if (b < nbr) {
-        const MergeBranch& mb = kTab ? tb[b] : a.br[b];
-        const int pn = (int)div_magic((uint32_t)p, mb.dg);
-        const int pt = p - pn * mb.g.g;
-        const int pi = (int)div_magic((uint32_t)pt, mb.dr);
-        const int pj = pt - pi * mb.g.r;
-        const int hpg = mb.g.hpg;
-        const int hf = pj * hpg;
-        const uint32_t rb = (uint32_t)(bidx * mb.g.nseg + pn);
-        const char* orow = reinterpret_cast<const char*>(mb.o) + (rb * (uint32_t)mb.g.m + (uint32_t)pi) * (uint32_t)(E * 2);
-        cv0[b] = (unsigned)(h0 - hf) < (unsigned)hpg;
-        cv1[b] = (unsigned)(h1 - hf) < (unsigned)hpg;
-        l0[b] = lse_s[t * LS + b * 16 + (cv0[b] ? h0 - hf : 0)];
-        l1[b] = lse_s[t * LS + b * 16 + (cv1[b] ? h1 - hf : 0)];
-        o0[b] = *reinterpret_cast<const uint4*>(orow + opaque_u32(cv0[b] ? 2 * c0 : 2 * D * hf));
-        o1[b] = *reinterpret_cast<const uint2*>(orow + opaque_u32(cv1[b] ? 2 * c1 : 2 * D * hf));
-      }
-    }
-    float mx0 = -INFINITY, mx1 = -INFINITY;
-#pragma unroll
-    for (int b = 0; b < NBR; ++b)
-      if (b < nbr) {
-        if (!cv0[b] || l0[b] == 0.f) l0[b] = -1e8f;   // dilated_attention.py:46
-        mx0 = fmaxf(mx0, l0[b]);
-        if (!cv1[b] || l1[b] == 0.f) l1[b] = -1e8f;
-        mx1 = fmaxf(mx1, l1[b]);
-      }
-    float ws0 = 0.f, ws1 = 0.f;
-#pragma unroll
-    for (int b = 0; b < NBR; ++b)
-      if (b < nbr) {
-        l0[b] = fast_exp2((l0[b] - mx0) * 1.44269504088896340736f);
-        ws0 += l0[b];
-        l1[b] = fast_exp2((l1[b] - mx1) * 1.44269504088896340736f);
-        ws1 += l1[b];
-      }
-    const float inv0 = __builtin_amdgcn_rcpf(ws0), inv1 = __builtin_amdgcn_rcpf(ws1);
-    float v[12];
-#pragma unroll
-    for (int e = 0; e < 12; ++e) v[e] = 0.f;
-#pragma unroll
-    for (int b = 0; b < NBR; ++b)
-      if (b < nbr) {
-        const float wb0 = cv0[b] ? l0[b] * inv0 : 0.f;
-        const float wb1 = cv1[b] ? l1[b] * inv1 : 0.f;
-        const uint32_t u0[4] = {o0[b].x, o0[b].y, o0[b].z, o0[b].w};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          v[2 * q] = __builtin_fmaf(e2f<kH>(u0[q]), wb0, v[2 * q]);
-          v[2 * q + 1] = __builtin_fmaf(e2f_hi<kH>(u0[q]), wb0, v[2 * q + 1]);
-        }
-        v[8] = __builtin_fmaf(e2f<kH>(o1[b].x), wb1, v[8]);
-        v[9] = __builtin_fmaf(e2f_hi<kH>(o1[b].x), wb1, v[9]);
-        v[10] = __builtin_fmaf(e2f<kH>(o1[b].y), wb1, v[10]);
-        v[11] = __builtin_fmaf(e2f_hi<kH>(o1[b].y), wb1, v[11]);
-      }
-    if (ln) {
-      float s = 0.f;
-#pragma unroll
-      for (int e = 0; e < 12; ++e) s += v[e];
-      const float mean = wave_sum_xor(s) * (1.0f / E);
-      float q = 0.f;
-#pragma unroll
-      for (int e = 0; e < 12; ++e) {
-        const float d = v[e] - mean;
-        q = __builtin_fmaf(d, d, q);
-      }
-      const float rstd = rsqrtf(__builtin_fmaf(wave_sum_xor(q), 1.0f / E, a.eps));
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = __builtin_fmaf((v[e] - mean) * rstd, w0[e], b0[e]);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[8 + e] = __builtin_fmaf((v[8 + e] - mean) * rstd, w1[e], b1[e]);
-    }
-    char* orow = reinterpret_cast<char*>(a.out) + (int64_t)row * (E * 2);
-    *reinterpret_cast<uint4*>(orow + 2 * c0) =
-        make_uint4(pack2e<kH>(v[0], v[1]), pack2e<kH>(v[2], v[3]), pack2e<kH>(v[4], v[5]), pack2e<kH>(v[6], v[7]));
-    *reinterpret_cast<uint2*>(orow + 2 * c1) = make_uint2(pack2e<kH>(v[8], v[9]), pack2e<kH>(v[10], v[11]));
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void dilated_gather_kernel(const uint16_t* __restrict__ src, int64_t row_stride,
-                                                             int64_t col_off, int64_t L, int H, int D, GpBranch g,
-                                                             int64_t total_rows, uint16_t* __restrict__ dst) {
-  const int CH = D / 8;
-  const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t row = id / CH;
-  if (row >= total_rows) return;
-  const int ch = (int)(id % CH);
-  const int i = (int)(row % g.m);
-  const int64_t t = row / g.m;
-  const int hh = (int)(t % H);
-  const int64_t bn = t / H;
-  const int64_t bidx = bn / g.nseg;
-  const int n = (int)(bn % g.nseg);
-  const int j = hh / g.hpg;
-  uint4 v = make_uint4(0, 0, 0, 0);
-  if (i < gp_valid_rows(g, L, n, j)) {
-    const int64_t tok = bidx * L + (int64_t)n * g.s + j + (int64_t)i * g.r;
-    v = *reinterpret_cast<const uint4*>(src + tok * row_stride + col_off + hh * D + ch * 8);
-  }
-  *reinterpret_cast<uint4*>(dst + row * D + ch * 8) = v;
-}
-
 }  // namespace
 
 // =========================================================================================
-extern "C" int gp_dilated_gather(const uint16_t* src, int64_t row_stride, int64_t col_off, int64_t B, int64_t L,
-                                 int H, int D, int sl, int r, uint16_t* dst, void* stream) {
-  GP_REQUIRE(B > 0 && L > 0 && H > 0 && D > 0 && sl > 0 && r > 0, "gp_dilated_gather: bad sizes");
-  GP_REQUIRE(D % 8 == 0 && row_stride % 8 == 0 && col_off % 8 == 0 && row_stride >= col_off + (int64_t)H * D,
-             "gp_dilated_gather: D, row_stride and col_off must be multiples of 8 elements");
-  GP_REQUIRE(src && dst && gp_aligned(src, 16) && gp_aligned(dst, 16), "gp_dilated_gather: pointers must be 16-byte aligned");
-  const GpBranch g = gp_make_branch(L, sl, r, H);
-  const int64_t rows = B * g.nseg * (int64_t)H * g.m;
-  const int64_t chunks = rows * (D / 8);
-  dilated_gather_kernel<<<(unsigned)((chunks + 255) / 256), 256, 0, gp_stream(stream)>>>(src, row_stride, col_off, L,
-                                                                                         H, D, g, rows, dst);
-  return gp_check_launch("gp_dilated_gather");
-}
-
-static int attn_num_cus(hipStream_t s) {     // per-device cache of the CU count
+int attn_num_cus(hipStream_t s) {            // per-device cache of the CU count (declared in gp_attn_plan.h)
   static int cache[64] = {0};
   int dev = 0;
   if (hipStreamGetDevice(s, &dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
@@ -1880,19 +1139,12 @@ static int attn_num_cus(hipStream_t s) {     // per-device cache of the CU count
 // An LDS-DMA launch whose 8-wave work items cannot fill the GPU (fewer items than the 3 per CU that are
 // resident at once: the long-branch launch of a sequence-parallel rank holds ~384 for 768 slots) runs 4-wave
 // workgroups of 128 queries instead -- twice the items, each K/V tile shared by half as many queries.  Same
-// per-query arithmetic: bit-identical outputs (round 5).  0 disables.
-#ifndef GP_ATTN_SMALL_LAUNCH_NW4
-#define GP_ATTN_SMALL_LAUNCH_NW4 1
-#endif
-// (8-wave items per CU below which a launch counts as under-filled)
-#ifndef GP_ATTN_SMALL_LAUNCH_PER_CU
-#define GP_ATTN_SMALL_LAUNCH_PER_CU 3
-#endif
+// per-query arithmetic: bit-identical outputs (round 5).
+constexpr int kSmallLaunchPerCU = 3;   // 8-wave items per CU below which a launch counts as under-filled
 
 extern "C" int gp_attn_launch_params(int32_t* params, int n) {
   GP_REQUIRE(params && n >= 0, "gp_attn_launch_params: null params");
-  const int32_t v[4] = {32 * kNWFast, GP_ATTN_FAST_WPS * 4 / kNWFast,
-                        GP_ATTN_SMALL_LAUNCH_NW4 ? GP_ATTN_SMALL_LAUNCH_PER_CU : 0, 64};
+  const int32_t v[4] = {32 * kNWFast, GP_ATTN_FAST_WPS * 4 / kNWFast, kSmallLaunchPerCU, 64};
   for (int i = 0; i < n && i < 4; ++i) params[i] = v[i];
   return 0;
 }
@@ -1943,9 +1195,8 @@ static int attn_fwd_impl(const uint16_t* q, int64_t q_row_stride, int64_t q_tok_
   hipStream_t s = gp_stream(stream);
   // query rows per workgroup; an under-filled 8-wave LDS-DMA launch of the bf16 / V-bf16 pair goes to 4 waves
   // (the item count is computed for 8 first, below)
-  const bool small_ok = GP_ATTN_SMALL_LAUNCH_NW4 && fast && kNWFast == 8 && (fmt == GP_FMT_BF16 || fmt == GP_FMT_F16_VBF16);
+  const bool small_ok = fast && kNWFast == 8 && (fmt == GP_FMT_BF16 || fmt == GP_FMT_F16_VBF16);
   int qblk = fast ? 32 * kNWFast : 128;
-  // order branches by keys per work item (descending) so the longest items start first
   int order[GP_MAX_BRANCHES];
   GpBranch geo[GP_MAX_BRANCHES];
   for (int b = 0; b < nbranch; ++b) {
@@ -1961,12 +1212,8 @@ static int attn_fwd_impl(const uint16_t* q, int64_t q_row_stride, int64_t q_tok_
     GP_REQUIRE(!d.kv_sparse_cols || H % d.ratio == 0, "gp_dilated_attn_fwd: sparse k/v columns need H %% r == 0");
     GP_REQUIRE(d.kv_row_stride >= (int64_t)(d.kv_sparse_cols ? geo[b].hpg : H) * D,
                "gp_dilated_attn_fwd: branch %d k/v row stride too small", b);
-    order[b] = b;
   }
-  for (int x = 1; x < nbranch; ++x)
-    for (int y = x; y > 0 && geo[order[y]].m > geo[order[y - 1]].m; --y) {
-      int tmp = order[y]; order[y] = order[y - 1]; order[y - 1] = tmp;
-    }
+  order_by_rows_desc(geo, nbranch, order);
   int64_t items = 0;
   auto plan_items = [&]() {
   items = 0;
@@ -2013,7 +1260,7 @@ static int attn_fwd_impl(const uint16_t* q, int64_t q_row_stride, int64_t q_tok_
   GP_REQUIRE(!parts || (fast && kNWFast == 8 && (fmt == GP_FMT_BF16 || fmt == GP_FMT_F16_VBF16)),
              "gp_dilated_attn_fwd: key parts need the LDS-DMA bf16 pair (D = 48, pre-scaled q, k / v in one layout)");
   bool nw4 = false;
-  if (small_ok && !parts && items < GP_ATTN_SMALL_LAUNCH_PER_CU * (int64_t)attn_num_cus(s)) {
+  if (small_ok && !parts && items < kSmallLaunchPerCU * (int64_t)attn_num_cus(s)) {
     qblk = 128;
     nw4 = true;
     plan_items();
@@ -2025,58 +1272,19 @@ static int attn_fwd_impl(const uint16_t* q, int64_t q_row_stride, int64_t q_tok_
   a.ntab = 0;
   a.ltab = nullptr;
   GP_REQUIRE(items < (int64_t)0x7fffffff, "gp_dilated_attn_fwd: too many work items");
-  if (parts) {   // key parts (sequence-parallel under-filled launches): the 8-wave pair built with parts
-    if (fmt == GP_FMT_F16_VBF16) {
-      dilated_attn32_kernel<48, true, kModeFast, false, 8, true, true><<<(unsigned)items, 512, 0, s>>>(a);
-      if constexpr (GP_ATTN_NOFIX == 0)
-        dilated_attn32_kernel<48, true, kModeFix, false, 8, true, true><<<(unsigned)((items + kFixItems - 1) / kFixItems), 512, 0, s>>>(a);
-    } else {
-      dilated_attn32_kernel<48, true, kModeFast, false, 8, false, true><<<(unsigned)items, 512, 0, s>>>(a);
-      if constexpr (GP_ATTN_NOFIX == 0)
-        dilated_attn32_kernel<48, true, kModeFix, false, 8, false, true><<<(unsigned)((items + kFixItems - 1) / kFixItems), 512, 0, s>>>(a);
-    }
-    return gp_check_launch("gp_dilated_attn_fwd");
-  }
-  if (nw4) {   // the under-filled launch in 4-wave workgroups (fast pair only)
-    if (fmt == GP_FMT_F16_VBF16) {
-      dilated_attn32_kernel<48, true, kModeFast, false, 4, true><<<(unsigned)items, 256, 0, s>>>(a);
-      if constexpr (GP_ATTN_NOFIX == 0)
-        dilated_attn32_kernel<48, true, kModeFix, false, 4, true><<<(unsigned)((items + kFixItems - 1) / kFixItems), 256, 0, s>>>(a);
-    } else {
-      dilated_attn32_kernel<48, true, kModeFast, false, 4><<<(unsigned)items, 256, 0, s>>>(a);
-      if constexpr (GP_ATTN_NOFIX == 0)
-        dilated_attn32_kernel<48, true, kModeFix, false, 4><<<(unsigned)((items + kFixItems - 1) / kFixItems), 256, 0, s>>>(a);
-    }
-    return gp_check_launch("gp_dilated_attn_fwd");
-  }
-  if (fmt == GP_FMT_F16_VBF16) {
-    // fp16 q / k, bf16 v: the bf16 product pair with the fp16 S MFMA (no max; fixup pass)
-    dilated_attn32_kernel<48, true, kModeFast, false, kNWFast, true><<<(unsigned)items, 64 * kNWFast, 0, s>>>(a);
-    if constexpr (GP_ATTN_NOFIX == 0)
-      dilated_attn32_kernel<48, true, kModeFix, false, kNWFast, true>
-          <<<(unsigned)((items + kFixItems - 1) / kFixItems), 64 * kNWFast, 0, s>>>(a);
+  if (fast && fmt != GP_FMT_F16) {
+    // the product pair (bf16, or fp16 q / k with the fp16 S MFMA and a bf16 v): with key parts (sequence-parallel
+    // under-filled launches, 8 waves), in 4-wave workgroups (other under-filled launches), or the default
+    const bool h = fmt == GP_FMT_F16_VBF16;
+    if (parts) h ? launch_fast_fix<false, 8, true, true>(a, s) : launch_fast_fix<false, 8, false, true>(a, s);
+    else if (nw4) h ? launch_fast_fix<false, 4, true>(a, s) : launch_fast_fix<false, 4, false>(a, s);
+    else h ? launch_fast_fix<false, kNWFast, true>(a, s) : launch_fast_fix<false, kNWFast, false>(a, s);
+  } else if (fast) {   // fp16 v: the exact running-max kernel
+    dilated_attn32_kernel<48, true, kModeExact, false, kNWFast, true><<<(unsigned)items, 64 * kNWFast, 0, s>>>(a);
   } else if (kh) {
-    if (fast) {        // fp16 v: the exact running-max kernel
-      dilated_attn32_kernel<48, true, kModeExact, false, kNWFast, true><<<(unsigned)items, 64 * kNWFast, 0, s>>>(a);
-    } else if (D == 96) dilated_attn_kernel<96, true><<<(unsigned)items, 256, 0, s>>>(a);
-    else if (D == 48 && q_log2_prescaled) dilated_attn32_kernel<48, true, kModeGen, false, 4, true><<<(unsigned)items, 256, 0, s>>>(a);
-    else if (D == 48) dilated_attn32_kernel<48, false, kModeGen, false, 4, true><<<(unsigned)items, 256, 0, s>>>(a);
-    else if (q_log2_prescaled) dilated_attn32_kernel<64, true, kModeGen, false, 4, true><<<(unsigned)items, 256, 0, s>>>(a);
-    else dilated_attn32_kernel<64, false, kModeGen, false, 4, true><<<(unsigned)items, 256, 0, s>>>(a);
-  } else if (D == 96) {
-    dilated_attn_kernel<96><<<(unsigned)items, 256, 0, s>>>(a);
-  } else if (fast) {
-    // the product launch: no-max kernel, then the fixup pass (exits at once unless a row was flagged)
-    dilated_attn32_kernel<48, true, kModeFast, false, kNWFast><<<(unsigned)items, 64 * kNWFast, 0, s>>>(a);
-    if constexpr (GP_ATTN_NOFIX == 0)
-      dilated_attn32_kernel<48, true, kModeFix, false, kNWFast>
-          <<<(unsigned)((items + kFixItems - 1) / kFixItems), 64 * kNWFast, 0, s>>>(a);
-  } else if (D == 48) {
-    if (q_log2_prescaled) dilated_attn32_kernel<48, true, kModeGen><<<(unsigned)items, 256, 0, s>>>(a);
-    else dilated_attn32_kernel<48, false, kModeGen><<<(unsigned)items, 256, 0, s>>>(a);
+    launch_attn_gen<true>(a, D, q_log2_prescaled != 0, s);
   } else {
-    if (q_log2_prescaled) dilated_attn32_kernel<64, true, kModeGen><<<(unsigned)items, 256, 0, s>>>(a);
-    else dilated_attn32_kernel<64, false, kModeGen><<<(unsigned)items, 256, 0, s>>>(a);
+    launch_attn_gen<false>(a, D, q_log2_prescaled != 0, s);
   }
   return gp_check_launch("gp_dilated_attn_fwd");
 }
@@ -2164,12 +1372,8 @@ extern "C" int gp_attn_rows_plan(const uint16_t* q, const uint16_t* k, const uin
     GP_REQUIRE(dv >= 0 && 2 * row_stride >= dv + 2 * D && dv + 64 * (int64_t)ratios[b] * 2 * row_stride < 0x7fffffff,
                "gp_attn_rows_plan: k / v must share one row layout (v at or after k)");
     geo[b] = gp_make_branch(L, seg_len[b], ratios[b], H);
-    order[b] = b;
   }
-  for (int x = 1; x < nbranch; ++x)
-    for (int y = x; y > 0 && geo[order[y]].m > geo[order[y - 1]].m; --y) {
-      int tmp = order[y]; order[y] = order[y - 1]; order[y - 1] = tmp;
-    }
+  order_by_rows_desc(geo, nbranch, order);
   const int qblk = 32 * kNWFast;
   AttnListEntry* tab = reinterpret_cast<AttnListEntry*>(static_cast<char*>(plan_host) + kRowsTabOff);
   int64_t items = 0, nent = 0;
@@ -2217,15 +1421,6 @@ extern "C" int gp_attn_rows_plan(const uint16_t* q, const uint16_t* k, const uin
   return 0;
 }
 
-// (4-wave blocks of 128 slots measured no faster on the 70k forward -- DESIGN §3.7 -- so one block size)
-template <bool kH>
-static void launch_attn_rows(const AttnArgs& a, hipStream_t s) {
-  constexpr int NW = kNWFast;
-  dilated_attn32_kernel<48, true, kModeFast, false, NW, kH, false, true><<<(unsigned)a.total_items, 64 * NW, 0, s>>>(a);
-  if constexpr (GP_ATTN_NOFIX == 0)
-    dilated_attn32_kernel<48, true, kModeFix, false, NW, kH, false, true><<<(unsigned)a.total_items, 64 * NW, 0, s>>>(a);
-}
-
 extern "C" int gp_dilated_attn_fwd_rows(const void* plan_host, const void* plan_dev, int q_log2_prescaled, int fmt,
                                         void* stream) {
   GP_REQUIRE(fmt == GP_FMT_BF16 || fmt == GP_FMT_F16_VBF16,
@@ -2248,7 +1443,9 @@ extern "C" int gp_dilated_attn_fwd_rows(const void* plan_host, const void* plan_
   a.ntab = h.nent;
   a.d_H = make_div_magic((uint32_t)h.H);
   hipStream_t s = gp_stream(stream);
-  if (fmt == GP_FMT_F16_VBF16) launch_attn_rows<true>(a, s); else launch_attn_rows<false>(a, s);
+  // (4-wave blocks of 128 slots measured no faster on the 70k forward -- DESIGN §3.7 -- so one block size)
+  if (fmt == GP_FMT_F16_VBF16) launch_fast_fix<false, kNWFast, true, false, true>(a, s);
+  else launch_fast_fix<false, kNWFast, false, false, true>(a, s);
   return gp_check_launch("gp_dilated_attn_fwd_rows");
 }
 
@@ -2282,163 +1479,9 @@ extern "C" int gp_seg_attn_fwd_f16(const uint16_t* q, const uint16_t* k, const u
   return seg_attn(q, k, v, nbatch, seqlen, H, D, softmax_scale, o, lse, true, stream);
 }
 
-extern "C" int gp_branch_merge_ln(const uint16_t* const* o_in, const float* const* lse_in, const int32_t* seg_len,
-                                  const int32_t* ratios, int nbranch, int64_t B, int64_t L, int H, int D,
-                                  const float* ln_w, const float* ln_b, float eps, uint16_t* out, int fmt,
-                                  void* stream) {
-  return gp_branch_merge_ln_window(o_in, lse_in, seg_len, ratios, nbranch, B, L, 0, L, H, D, ln_w, ln_b, eps, out,
-                                   fmt, stream);
-}
-
-// the E = 768 / D = 48 merge: one token per wave, 4 waves per block
-static unsigned merge_v2_grid(int64_t tokens) { return (unsigned)((tokens + GP_MERGE_WPB - 1) / GP_MERGE_WPB); }
-// its 32-bit byte offsets: every branch's o rows (B * nseg * m rows of 1,536 B) below 4 GiB
-static bool merge_v2_fits(const MergeArgs& a) {
-  for (int b = 0; b < a.nbranch; ++b)
-    if ((uint64_t)a.B * a.br[b].g.nseg * a.br[b].g.m * 1536u >= (1ull << 32)) return false;
-  return true;
-}
-
-template <bool kH>
-static void launch_merge(const MergeArgs& a, int E, int D, int nbranch, unsigned nb, hipStream_t s) {
-  switch (E) {
-    case 768:
-      // (5 entries only: the 7 / 8-entry instantiations need 134-145 VGPRs and spill SGPRs; they keep the v2 kernel)
-      if (GP_MERGE_V3 != 0 && D == 48 && nbranch == 5 && merge_v2_fits(a)) {
-        // tokens per block: the blocks spread evenly over the CUs -- the kernel is bound per CU (outstanding L2
-        // requests), so a CU holding one block more than another finishes a block's time later (70k: 9 blocks of
-        // 31 tokens per CU; 256k: 32 blocks of 32)
-        const int64_t T = a.B * a.ntok;
-        const int64_t ncu = attn_num_cus(s);
-        const int64_t per_cu = (T + ncu * kV3Tok - 1) / (ncu * kV3Tok);
-        const int tpb = (int)std::max<int64_t>(1, (T + ncu * per_cu - 1) / (ncu * per_cu));
-        const unsigned g = (unsigned)((T + tpb - 1) / tpb);
-        branch_merge_v3_kernel<5, kH><<<g, 256, 0, s>>>(a, tpb);
-      } else if (D == 48 && merge_v2_fits(a)) {
-        const unsigned g = merge_v2_grid(a.B * a.ntok);
-        if (nbranch == 5) branch_merge_v2_kernel<5, false, kH><<<g, 64 * GP_MERGE_WPB, 0, s>>>(a);
-        // (5 branches, two of them in two key parts: the sequence-parallel long-branch split, seqpar.plan_key_parts)
-        else if (nbranch == 7) branch_merge_v2_kernel<7, false, kH><<<g, 64 * GP_MERGE_WPB, 0, s>>>(a);
-        else branch_merge_v2_kernel<GP_MAX_BRANCHES, false, kH><<<g, 64 * GP_MERGE_WPB, 0, s>>>(a);
-      } else if (D == 96) branch_merge_kernel<12, 96, false, GP_MAX_BRANCHES, kH><<<nb, 256, 0, s>>>(a);
-      else branch_merge_kernel<12, 12, false, GP_MAX_BRANCHES, kH><<<nb, 256, 0, s>>>(a);
-      break;
-    case 1024:
-      if (D == 64) branch_merge_kernel<16, 64, false, GP_MAX_BRANCHES, kH><<<nb, 256, 0, s>>>(a);
-      else branch_merge_kernel<16, 16, false, GP_MAX_BRANCHES, kH><<<nb, 256, 0, s>>>(a);
-      break;
-    case 1536:
-      if (D == 96) branch_merge_kernel<24, 96, false, GP_MAX_BRANCHES, kH><<<nb, 256, 0, s>>>(a);
-      else if (D == 48) branch_merge_kernel<24, 48, false, GP_MAX_BRANCHES, kH><<<nb, 256, 0, s>>>(a);
-      else branch_merge_kernel<24, 24, false, GP_MAX_BRANCHES, kH><<<nb, 256, 0, s>>>(a);
-      break;
-  }
-}
-
-extern "C" int gp_branch_merge_ln_window(const uint16_t* const* o_in, const float* const* lse_in,
-                                         const int32_t* seg_len, const int32_t* ratios, int nbranch, int64_t B,
-                                         int64_t L, int64_t tok_lo, int64_t n_tok, int H, int D, const float* ln_w,
-                                         const float* ln_b, float eps, uint16_t* out, int fmt, void* stream) {
-  const int E = H * D;
-  GP_REQUIRE(fmt == GP_FMT_BF16 || fmt == GP_FMT_F16, "gp_branch_merge_ln: bad fmt %d", fmt);
-  GP_REQUIRE(nbranch >= 1 && nbranch <= GP_MAX_BRANCHES, "gp_branch_merge_ln: nbranch must be 1..%d", GP_MAX_BRANCHES);
-  GP_REQUIRE((E == 768 && (D == 48 || D == 96 || D == 12)) || (E == 1024 && (D == 64 || D == 16)) ||
-                 (E == 1536 && (D == 96 || D == 48 || D == 24)),
-             "gp_branch_merge_ln: H*D=%d with D=%d unsupported", E, D);
-  GP_REQUIRE(B * L < (int64_t)0x7fffffff, "gp_branch_merge_ln: B*L too large");
-  GP_REQUIRE(B > 0 && L > 0 && tok_lo >= 0 && n_tok >= 0 && tok_lo + n_tok <= L, "gp_branch_merge_ln: bad sizes");
-  if (n_tok == 0) return 0;
-  GP_REQUIRE(o_in && lse_in && seg_len && ratios && out, "gp_branch_merge_ln: null pointer");
-  GP_REQUIRE(ln_w == nullptr || ln_b != nullptr, "gp_branch_merge_ln: ln_w without ln_b");
-  MergeArgs a;
-  a.B = B; a.L = L; a.H = H; a.D = D; a.E = E; a.nbranch = nbranch;
-  a.tok_lo = tok_lo; a.ntok = n_tok;
-  a.dnt = make_div_magic((uint32_t)n_tok);
-  a.tok_list = nullptr;
-  for (int b = 0; b < nbranch; ++b) {
-    GP_REQUIRE(seg_len[b] > 0 && ratios[b] > 0 && o_in[b] && lse_in[b], "gp_branch_merge_ln: bad branch %d", b);
-    a.br[b].g = gp_make_branch(L, seg_len[b], ratios[b], H);
-    a.br[b].o = o_in[b];
-    a.br[b].lse = lse_in[b];
-    merge_branch_magic(a.br[b]);
-  }
-  for (int b = nbranch; b < GP_MAX_BRANCHES; ++b) a.br[b] = a.br[nbranch - 1];
-  a.ln_w = ln_w; a.ln_b = ln_b; a.eps = eps; a.out = out;
-  const unsigned nb = (unsigned)((B * n_tok + 4 * kTPW - 1) / (4 * kTPW));   // kTPW tokens per wave
-  if (fmt == GP_FMT_F16) launch_merge<true>(a, E, D, nbranch, nb, gp_stream(stream));
-  else launch_merge<false>(a, E, D, nbranch, nb, gp_stream(stream));
-  return gp_check_launch("gp_branch_merge_ln");
-}
-
-// the listed-token merge runs on branch_merge_v3_kernel alone: E = 768, D = 48, five branch entries
-extern "C" int gp_branch_merge_ln_rows_supported(int H, int D, int nbranch) {
-  return GP_MERGE_V3 != 0 && H == 16 && D == 48 && nbranch == 5;
-}
-
-extern "C" int gp_branch_merge_ln_rows(const uint16_t* const* o_in, const float* const* lse_in,
-                                       const int32_t* seg_len, const int32_t* ratios, int nbranch, int64_t B,
-                                       int64_t L, const int32_t* rows, int64_t n_rows, int H, int D,
-                                       const float* ln_w, const float* ln_b, float eps, uint16_t* out, int fmt,
-                                       void* stream) {
-  GP_REQUIRE(fmt == GP_FMT_BF16 || fmt == GP_FMT_F16, "gp_branch_merge_ln_rows: bad fmt %d", fmt);
-  GP_REQUIRE(gp_branch_merge_ln_rows_supported(H, D, nbranch),
-             "gp_branch_merge_ln_rows: H %d, D %d, %d branches unsupported (16, 48, 5)", H, D, nbranch);
-  GP_REQUIRE(B * L < (int64_t)0x7fffffff, "gp_branch_merge_ln_rows: B*L too large");
-  GP_REQUIRE(B > 0 && L > 0 && n_rows >= 0 && n_rows <= L, "gp_branch_merge_ln_rows: bad sizes");
-  if (n_rows == 0) return 0;
-  GP_REQUIRE(o_in && lse_in && seg_len && ratios && rows && out, "gp_branch_merge_ln_rows: null pointer");
-  GP_REQUIRE(ln_w == nullptr || ln_b != nullptr, "gp_branch_merge_ln_rows: ln_w without ln_b");
-  GP_REQUIRE(gp_aligned(out, 16), "gp_branch_merge_ln_rows: out must be 16-byte aligned");
-  MergeArgs a;
-  a.B = B; a.L = L; a.H = H; a.D = D; a.E = H * D; a.nbranch = nbranch;
-  a.tok_lo = 0; a.ntok = n_rows;
-  a.dnt = make_div_magic((uint32_t)n_rows);
-  a.tok_list = rows;
-  for (int b = 0; b < nbranch; ++b) {
-    GP_REQUIRE(seg_len[b] > 0 && ratios[b] > 0 && o_in[b] && lse_in[b], "gp_branch_merge_ln_rows: bad branch %d", b);
-    a.br[b].g = gp_make_branch(L, seg_len[b], ratios[b], H);
-    a.br[b].o = o_in[b];
-    a.br[b].lse = lse_in[b];
-    merge_branch_magic(a.br[b]);
-  }
-  for (int b = nbranch; b < GP_MAX_BRANCHES; ++b) a.br[b] = a.br[nbranch - 1];
-  GP_REQUIRE(merge_v2_fits(a), "gp_branch_merge_ln_rows: a branch's o rows pass 4 GiB");
-  a.ln_w = ln_w; a.ln_b = ln_b; a.eps = eps; a.out = out;
-  a.mtab = nullptr; a.tok_off = nullptr; a.nslide = 0;
-  hipStream_t s = gp_stream(stream);
-  // tokens per block as launch_merge spreads them: whole blocks per CU
-  const int64_t T = B * n_rows;
-  const int64_t ncu = attn_num_cus(s);
-  const int64_t per_cu = (T + ncu * kV3Tok - 1) / (ncu * kV3Tok);
-  const int tpb = (int)std::max<int64_t>(1, (T + ncu * per_cu - 1) / (ncu * per_cu));
-  const unsigned g = (unsigned)((T + tpb - 1) / tpb);
-  if (fmt == GP_FMT_F16) branch_merge_v3_kernel<5, true, false, true><<<g, 256, 0, s>>>(a, tpb);
-  else branch_merge_v3_kernel<5, false, false, true><<<g, 256, 0, s>>>(a, tpb);
-  return gp_check_launch("gp_branch_merge_ln_rows");
-}
-
 // =========================================================================================
-// Varlen packing (config C5): several slides concatenated token-major in one [T, 3E] qkv buffer
-// (slide i at rows [tok_off[i], tok_off[i] + L_i)), one attention launch and one merge launch
-// for all of them.  Every slide keeps its own segment schedule (s = min(sl, L_i), ...) and no
-// query attends across slides, so each slide's outputs are those of its own B = 1 forward.
-// The plan (host bytes, copied by the caller to device memory) holds the work table.
-namespace {
-constexpr int32_t kVarlenMagic = 0x47505631;   // "GPV1"
-struct VarlenHdr {
-  int32_t magic, nslide, nbranch, H, D, ntab;
-  int64_t T, total_items, qkv_stride;
-  int64_t tab_off, mtab_off, tok_off_off, bytes;
-};
-inline int64_t gp_align16(int64_t x) { return (x + 15) & ~int64_t(15); }
-inline void varlen_layout(int nslide, int nbranch, VarlenHdr& h) {
-  h.tab_off = gp_align16(sizeof(VarlenHdr));
-  h.mtab_off = gp_align16(h.tab_off + (int64_t)nslide * nbranch * sizeof(AttnBranch));
-  h.tok_off_off = gp_align16(h.mtab_off + (int64_t)nslide * nbranch * sizeof(MergeBranch));
-  h.bytes = gp_align16(h.tok_off_off + (int64_t)(nslide + 1) * sizeof(int64_t));
-}
-}  // namespace
-
+// Varlen packing (packed slides, config C5): the plan's layout and purpose are in gp_attn_plan.h; its merge
+// launch is gp_branch_merge_ln_varlen (gp_merge.hip).
 extern "C" int64_t gp_varlen_plan_bytes(int nslide, int nbranch) {
   if (nslide < 1 || nbranch < 1 || nbranch > GP_MAX_BRANCHES) return -1;
   VarlenHdr h;
@@ -2539,19 +1582,13 @@ extern "C" int gp_varlen_plan(const int64_t* L, int nslide, int H, int D, const 
   return 0;
 }
 
-static int varlen_header(const void* plan_host, const void* plan_dev, const char* who, VarlenHdr& h) {
-  GP_REQUIRE(plan_host && plan_dev && gp_aligned(plan_dev, 16), "%s: null/misaligned plan", who);
-  h = *static_cast<const VarlenHdr*>(plan_host);
-  GP_REQUIRE(h.magic == kVarlenMagic, "%s: not a gp_varlen_plan buffer", who);
-  return 0;
-}
-
 extern "C" int gp_dilated_attn_fwd_varlen(const void* plan_host, const void* plan_dev, int q_log2_prescaled,
                                           int fmt, void* stream) {
   GP_REQUIRE(fmt == GP_FMT_BF16 || fmt == GP_FMT_F16 || fmt == GP_FMT_F16_VBF16, "gp_dilated_attn_fwd_varlen: bad fmt %d",
              fmt);
-  VarlenHdr h;
-  if (int rc = varlen_header(plan_host, plan_dev, "gp_dilated_attn_fwd_varlen", h)) return rc;
+  GP_REQUIRE(plan_host && plan_dev && gp_aligned(plan_dev, 16), "gp_dilated_attn_fwd_varlen: null/misaligned plan");
+  const VarlenHdr h = *static_cast<const VarlenHdr*>(plan_host);
+  GP_REQUIRE(h.magic == kVarlenMagic, "gp_dilated_attn_fwd_varlen: not a gp_varlen_plan buffer");
   GP_REQUIRE(h.D == 48 && q_log2_prescaled, "gp_dilated_attn_fwd_varlen: needs D = 48 and a pre-scaled q (D=%d)", h.D);
   if (h.total_items == 0) return 0;
   AttnArgs a;
@@ -2564,176 +1601,11 @@ extern "C" int gp_dilated_attn_fwd_varlen(const void* plan_host, const void* pla
   a.tab = reinterpret_cast<const AttnBranch*>(static_cast<const char*>(plan_dev) + h.tab_off);
   a.ntab = h.ntab;
   a.d_H = make_div_magic((uint32_t)h.H);
-  // the single-slide default's variant, so each packed slide's outputs equal its own launch's
-  if (fmt == GP_FMT_F16) {
-    dilated_attn32_kernel<48, true, kModeExact, true, kNWFast, true>
-        <<<(unsigned)h.total_items, 64 * kNWFast, 0, gp_stream(stream)>>>(a);
-    return gp_check_launch("gp_dilated_attn_fwd_varlen");
-  }
-  if (fmt == GP_FMT_F16_VBF16) {
-    dilated_attn32_kernel<48, true, kModeFast, true, kNWFast, true>
-        <<<(unsigned)h.total_items, 64 * kNWFast, 0, gp_stream(stream)>>>(a);
-    dilated_attn32_kernel<48, true, kModeFix, true, kNWFast, true>
-        <<<(unsigned)((h.total_items + kFixItems - 1) / kFixItems), 64 * kNWFast, 0, gp_stream(stream)>>>(a);
-    return gp_check_launch("gp_dilated_attn_fwd_varlen");
-  }
-  dilated_attn32_kernel<48, true, kModeFast, true, kNWFast><<<(unsigned)h.total_items, 64 * kNWFast, 0, gp_stream(stream)>>>(a);
-  dilated_attn32_kernel<48, true, kModeFix, true, kNWFast>
-      <<<(unsigned)((h.total_items + kFixItems - 1) / kFixItems), 64 * kNWFast, 0, gp_stream(stream)>>>(a);
-  return gp_check_launch("gp_dilated_attn_fwd_varlen");
-}
-
-extern "C" int gp_branch_merge_ln_varlen(const void* plan_host, const void* plan_dev, const float* ln_w,
-                                         const float* ln_b, float eps, uint16_t* out, int fmt, void* stream) {
-  GP_REQUIRE(fmt == GP_FMT_BF16 || fmt == GP_FMT_F16, "gp_branch_merge_ln_varlen: bad fmt %d", fmt);
-  VarlenHdr h;
-  if (int rc = varlen_header(plan_host, plan_dev, "gp_branch_merge_ln_varlen", h)) return rc;
-  GP_REQUIRE(h.H * h.D == 768 && h.D == 48, "gp_branch_merge_ln_varlen: needs H*D = 768, D = 48");
-  GP_REQUIRE(out && (ln_w == nullptr || ln_b != nullptr), "gp_branch_merge_ln_varlen: bad output / LN arguments");
-  MergeArgs a;
-  memset(&a, 0, sizeof(a));
-  a.B = 1; a.L = h.T; a.tok_lo = 0; a.ntok = h.T;
-  a.H = h.H; a.D = h.D; a.E = h.H * h.D; a.nbranch = h.nbranch;
-  a.ln_w = ln_w; a.ln_b = ln_b; a.eps = eps; a.out = out;
-  a.mtab = reinterpret_cast<const MergeBranch*>(static_cast<const char*>(plan_dev) + h.mtab_off);
-  a.tok_off = reinterpret_cast<const int64_t*>(static_cast<const char*>(plan_dev) + h.tok_off_off);
-  a.nslide = h.nslide;
-  // (the v2 kernel's 32-bit offsets run from each slide's own o / lse region: a slide's branch rows
-  // are at most 2 L_i, below 4 GiB for any slide the 1000 x 1000 position grid admits)
-  const unsigned nb = merge_v2_grid(h.T);
   hipStream_t s = gp_stream(stream);
-  if constexpr (GP_MERGE_V3_TAB != 0 && GP_MERGE_V3 != 0) if (h.nbranch == 5) {
-    // the v3 merge over the packed tokens when every slide holds at least a block's tokens (a block then meets at
-    // most two slides); tokens per block as the single-slide launch
-    const int64_t* toh = reinterpret_cast<const int64_t*>(static_cast<const char*>(plan_host) + h.tok_off_off);
-    int64_t shortest = INT64_MAX;
-    for (int i = 0; i < h.nslide; ++i) shortest = std::min<int64_t>(shortest, toh[i + 1] - toh[i]);
-    const int64_t ncu = attn_num_cus(s);
-    const int64_t per_cu = (h.T + ncu * kV3Tok - 1) / (ncu * kV3Tok);
-    const int tpb = (int)std::max<int64_t>(1, (h.T + ncu * per_cu - 1) / (ncu * per_cu));
-    if (shortest >= tpb) {
-      const unsigned g = (unsigned)((h.T + tpb - 1) / tpb);
-      if (fmt == GP_FMT_F16) branch_merge_v3_kernel<5, true, true><<<g, 256, 0, s>>>(a, tpb);
-      else branch_merge_v3_kernel<5, false, true><<<g, 256, 0, s>>>(a, tpb);
-      return gp_check_launch("gp_branch_merge_ln_varlen");
-    }
-  }
-  if (h.nbranch == 5) {   // every registered arch's schedule: compile-time branch loops
-    if (fmt == GP_FMT_F16) branch_merge_v2_kernel<5, true, true><<<nb, 64 * GP_MERGE_WPB, 0, s>>>(a);
-    else branch_merge_v2_kernel<5, true, false><<<nb, 64 * GP_MERGE_WPB, 0, s>>>(a);
-  } else if (fmt == GP_FMT_F16) {
-    branch_merge_v2_kernel<GP_MAX_BRANCHES, true, true><<<nb, 64 * GP_MERGE_WPB, 0, s>>>(a);
-  } else {
-    branch_merge_v2_kernel<GP_MAX_BRANCHES, true, false><<<nb, 64 * GP_MERGE_WPB, 0, s>>>(a);
-  }
-  return gp_check_launch("gp_branch_merge_ln_varlen");
-}
-
-// =========================================================================================
-// Token-major sparsified K/V rows for sequence parallelism (the per-rank half of
-// DilatedAttention.gathering, dilated_attention.py:16-31,76-98): for branch b, token p of
-// segment n = p / s sits at offset t = p % s, in head group j = t % r (sparse row t / r).  Its
-// row of dst[b] keeps only that group's hpg*D = C columns: [K cols j*C .. | V cols j*C ..], so a
-// contiguous token range of dst[b] is exactly what another rank's queries need from it.
-namespace {
-struct SparsifyArgs {
-  const uint16_t* src;
-  int64_t src_stride, k_col, v_col;
-  int64_t tok_lo, ntok, L;
-  int32_t nbranch, per_tok;            // 16-byte chunks per token over all branches
-  int32_t s[GP_MAX_BRANCHES], r[GP_MAX_BRANCHES], C[GP_MAX_BRANCHES], cbeg[GP_MAX_BRANCHES + 1];
-  int32_t ndest[GP_MAX_BRANCHES];
-  int64_t lo[GP_MAX_BRANCHES][GP_MAX_DESTS], hi[GP_MAX_BRANCHES][GP_MAX_DESTS];
-  uint16_t* dst[GP_MAX_BRANCHES][GP_MAX_DESTS];   // row of token lo
-};
-
-__global__ __launch_bounds__(256) void dilated_sparsify_kernel(const SparsifyArgs a) {
-  const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t t = id / a.per_tok;
-  if (t >= a.ntok) return;
-  int rem = (int)(id - t * a.per_tok);
-  int b = 0;
-#pragma unroll
-  for (int x = 1; x < GP_MAX_BRANCHES; ++x)
-    if (x < a.nbranch && rem >= a.cbeg[x]) b = x;
-  rem -= a.cbeg[b];
-  const int C = a.C[b];
-  const int half = C / 8;                      // chunks per K (or V) part
-  const int kv = rem >= half;
-  const int ch = rem - kv * half;
-  const int64_t p = a.tok_lo + t;
-  const int j = (int)(p % a.s[b]) % a.r[b];
-  const uint4 v = *reinterpret_cast<const uint4*>(a.src + t * a.src_stride + (kv ? a.v_col : a.k_col) + (int64_t)j * C + ch * 8);
-  for (int d = 0; d < a.ndest[b]; ++d)
-    if (p >= a.lo[b][d] && p < a.hi[b][d])
-      *reinterpret_cast<uint4*>(a.dst[b][d] + (p - a.lo[b][d]) * (2 * (int64_t)C) + kv * C + ch * 8) = v;
-}
-}  // namespace
-
-extern "C" int gp_dilated_sparsify_dests(const uint16_t* src, int64_t src_row_stride, int64_t k_col, int64_t v_col,
-                                         int64_t tok_lo, int64_t n_tok, int64_t L, int H, int D,
-                                         const int32_t* seg_len, const int32_t* ratios, int nbranch,
-                                         const GpRowDest* dests, const int32_t* ndest, void* stream) {
-  GP_REQUIRE(nbranch >= 1 && nbranch <= GP_MAX_BRANCHES, "gp_dilated_sparsify: nbranch must be 1..%d", GP_MAX_BRANCHES);
-  GP_REQUIRE(L > 0 && H > 0 && D > 0 && D % 8 == 0 && tok_lo >= 0 && n_tok >= 0 && tok_lo + n_tok <= L,
-             "gp_dilated_sparsify: bad sizes");
-  GP_REQUIRE(src_row_stride % 8 == 0 && k_col % 8 == 0 && v_col % 8 == 0, "gp_dilated_sparsify: strides must be multiples of 8");
-  if (n_tok == 0) return 0;
-  GP_REQUIRE(src && seg_len && ratios && dests && ndest && gp_aligned(src, 16), "gp_dilated_sparsify: null or misaligned pointer");
-  SparsifyArgs a;
-  a.src = src; a.src_stride = src_row_stride; a.k_col = k_col; a.v_col = v_col;
-  a.tok_lo = tok_lo; a.ntok = n_tok; a.L = L; a.nbranch = nbranch;
-  int cb = 0;
-  for (int b = 0; b < GP_MAX_BRANCHES; ++b) {
-    a.ndest[b] = 0;
-    for (int d = 0; d < GP_MAX_DESTS; ++d) { a.lo[b][d] = 0; a.hi[b][d] = 0; a.dst[b][d] = nullptr; }
-  }
-  for (int b = 0; b < nbranch; ++b) {
-    GP_REQUIRE(seg_len[b] > 0 && ratios[b] > 0 && H % ratios[b] == 0, "gp_dilated_sparsify: branch %d needs H %% r == 0", b);
-    GP_REQUIRE(ndest[b] >= 0 && ndest[b] <= GP_MAX_DESTS, "gp_dilated_sparsify: branch %d has %d destinations (max %d)",
-               b, ndest[b], GP_MAX_DESTS);
-    a.s[b] = (int32_t)(seg_len[b] < L ? seg_len[b] : L);
-    a.r[b] = ratios[b];
-    a.C[b] = (H / ratios[b]) * D;
-    a.ndest[b] = ndest[b];
-    for (int d = 0; d < ndest[b]; ++d) {
-      const GpRowDest& e = dests[b * GP_MAX_DESTS + d];
-      GP_REQUIRE(e.tok_lo <= e.tok_hi && (e.tok_lo == e.tok_hi || (e.dst && gp_aligned(e.dst, 16))),
-                 "gp_dilated_sparsify: branch %d destination %d null/misaligned or empty range", b, d);
-      a.lo[b][d] = e.tok_lo;
-      a.hi[b][d] = e.tok_hi;
-      a.dst[b][d] = e.dst;
-    }
-    a.cbeg[b] = cb;
-    cb += 2 * a.C[b] / 8;
-  }
-  for (int b = nbranch; b < GP_MAX_BRANCHES; ++b) { a.s[b] = 1; a.r[b] = 1; a.C[b] = 8; a.cbeg[b] = cb; }
-  a.cbeg[GP_MAX_BRANCHES] = cb;
-  a.per_tok = cb;
-  const int64_t work = n_tok * cb;
-  GP_REQUIRE(work / 256 < (int64_t)0x7fffffff, "gp_dilated_sparsify: too much work");
-  dilated_sparsify_kernel<<<(unsigned)((work + 255) / 256), 256, 0, gp_stream(stream)>>>(a);
-  return gp_check_launch("gp_dilated_sparsify");
-}
-
-extern "C" int gp_dilated_sparsify(const uint16_t* src, int64_t src_row_stride, int64_t k_col, int64_t v_col,
-                                   int64_t tok_lo, int64_t n_tok, int64_t L, int H, int D, const int32_t* seg_len,
-                                   const int32_t* ratios, int nbranch, uint16_t* const* dst,
-                                   const int64_t* dst_tok_base, void* stream) {
-  GP_REQUIRE(nbranch >= 1 && nbranch <= GP_MAX_BRANCHES, "gp_dilated_sparsify: nbranch must be 1..%d", GP_MAX_BRANCHES);
-  GP_REQUIRE(dst && seg_len && ratios, "gp_dilated_sparsify: null pointer");
-  GpRowDest dests[GP_MAX_BRANCHES * GP_MAX_DESTS];
-  int32_t nd[GP_MAX_BRANCHES];
-  for (int b = 0; b < nbranch; ++b) {
-    GP_REQUIRE(ratios[b] > 0 && H > 0 && H % ratios[b] == 0, "gp_dilated_sparsify: branch %d needs H %% r == 0", b);
-    const int64_t base = dst_tok_base ? dst_tok_base[b] : 0;
-    GP_REQUIRE(base <= tok_lo, "gp_dilated_sparsify: branch %d dst_tok_base beyond tok_lo", b);
-    const int64_t C = (int64_t)(H / ratios[b]) * D;
-    dests[b * GP_MAX_DESTS].tok_lo = tok_lo;
-    dests[b * GP_MAX_DESTS].tok_hi = tok_lo + n_tok;
-    dests[b * GP_MAX_DESTS].dst = dst[b] ? dst[b] + (tok_lo - base) * 2 * C : nullptr;
-    nd[b] = 1;
-  }
-  return gp_dilated_sparsify_dests(src, src_row_stride, k_col, v_col, tok_lo, n_tok, L, H, D, seg_len, ratios,
-                                   nbranch, dests, nd, stream);
+  // the single-slide default's variant, so each packed slide's outputs equal its own launch's
+  if (fmt == GP_FMT_F16)
+    dilated_attn32_kernel<48, true, kModeExact, true, kNWFast, true><<<(unsigned)h.total_items, 64 * kNWFast, 0, s>>>(a);
+  else if (fmt == GP_FMT_F16_VBF16) launch_fast_fix<true, kNWFast, true>(a, s);
+  else launch_fast_fix<true, kNWFast, false>(a, s);
+  return gp_check_launch("gp_dilated_attn_fwd_varlen");
 }
