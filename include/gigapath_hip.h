@@ -337,6 +337,48 @@ int gp_dilated_attn_fwd_varlen(const void* plan_host, const void* plan_dev, int 
 int gp_branch_merge_ln_varlen(const void* plan_host, const void* plan_dev, const float* ln_w,
                               const float* ln_b, float eps, uint16_t* out, int fmt, void* stream);
 
+/* ---- Backward of the packed attention (additive to ABI 13): (dq, dk, dv) of gp_dilated_attn_fwd_varlen + the
+ * no-LN gp_branch_merge_ln_varlen with respect to the packed q | k | v, given dmerged [T, H*D].  Per slide it is
+ * gp_dilated_attn_bwd of that slide alone (B = 1, L = L[i], q_log2_prescaled = 1): the same kernels and tile loops
+ * reached through a third addressing, so a slide's rows carry the bits of its own call.  D = 48 only, and q must
+ * be the pre-scaled q' the forward received (the gradient is taken with respect to it).
+ * Replaces: one gp_dilated_attn_bwd call per slide (13 launches each) by 13 launches for the whole pack.
+ *
+ * gp_varlen_bwd_plan_bytes: size of the host plan buffer (-1 on bad arguments).
+ * gp_varlen_bwd_plan: L / nslide / H / D / seg_len / ratios / nbranch / qkv / qkv_row_stride as gp_varlen_plan's;
+ *   o_in / lse_in: HOST tables of the nbranch packed per-branch buffers the forward wrote (sized and laid out by
+ *   gp_varlen_plan: slide-major [nseg_ib, m_ib, H, D] and [nseg_ib, H, m_ib] regions).  Always writes
+ *   *workspace_bytes: per branch the packed 16-bit dout_b and fp32 delta_b (the layouts of o and lse), then three
+ *   fp32 [T, H*D] accumulators, each rounded up to 256 bytes.  With plan_host == NULL that is all it does (qkv /
+ *   o_in / lse_in may be NULL).  Otherwise it fills plan_host (8-byte aligned; device pointers are stored, not
+ *   dereferenced); the caller copies the plan_bytes to a 16-byte aligned device buffer (plan_dev) that stays alive,
+ *   with qkv and the o / lse buffers, while launches use it.  The buffer begins with
+ *     int32 magic, nslide, nbranch, H, D, reserved; int64 T; int64 items[GP_MAX_BRANCHES]
+ *   (items[b]: work items of branch b's two attention launches, sum_i nseg_ib * H * ceil(m_ib / 128)); the rest
+ *   is private.
+ * gp_dilated_attn_bwd_varlen: dmerged [T, H*D] in fmt, contiguous; dq / dk / dv: rows of d_row_stride elements (>=
+ *   H*D, a multiple of 8; a fused [T, 3E] dqkv passes base, base + E, base + 2E and 3E).  fmt: GP_FMT_BF16 or
+ *   GP_FMT_F16, the format of qkv (GP_FMT_F16_VBF16 is rejected).
+ *   - Branch weights, zero pads, the recomputed P, the delta correction and the accumulation are
+ *     gp_dilated_attn_bwd's; every row limit (valid keys, rows that carry a dout, zero-pad keys) is taken against
+ *     the slide's own L[i]: no row of a neighbouring slide is read, whatever it holds.
+ *   - Every element of dq / dk / dv for packed rows [0, T) and all H*D columns is written (0 where no branch covers
+ *     the (token, head)); nothing else is.  No atomics: two calls give the same bits.
+ *   - A non-finite dmerged yields non-finite gradients in the rows of its slide and leaves the other slides' bits
+ *     as they are.
+ *   workspace: *workspace_bytes bytes, 16-byte aligned.  All pointers 16-byte aligned (lse_in entries 4).  Every
+ *   argument error (null or misaligned pointers, T or a branch's item count >= 2^31, a workspace that is too
+ *   small, a buffer that is not a backward plan) is rejected before any launch; the launch call copies nothing
+ *   from host to device.  Launches: a memset of the accumulators, the merge backward, two attention kernels per
+ *   branch, the store -- whatever nslide is. */
+int64_t gp_varlen_bwd_plan_bytes(int nslide, int nbranch);
+int gp_varlen_bwd_plan(const int64_t* L, int nslide, int H, int D, const int32_t* seg_len, const int32_t* ratios,
+                       int nbranch, const uint16_t* qkv, int64_t qkv_row_stride, const uint16_t* const* o_in,
+                       const float* const* lse_in, void* plan_host, int64_t plan_bytes, int64_t* workspace_bytes);
+int gp_dilated_attn_bwd_varlen(const void* plan_host, const void* plan_dev, const uint16_t* dmerged, uint16_t* dq,
+                               uint16_t* dk, uint16_t* dv, int64_t d_row_stride, void* workspace,
+                               size_t workspace_bytes, int fmt, void* stream);
+
 /* ---- The CLS row of the last layer's attention (ABI 11).  With global_pool off the slide readout
  * (slide_encoder.py:213-221, outcome = self.norm(x)[:, 0]) reads one row per slide from each layer, so
  * the last layer's DilatedAttention.forward (dilated_attention.py:133-217) is needed for the CLS token

@@ -31,7 +31,16 @@
 // merge_bwd_kernel writes dout_b = w_b dmerged first; the branches then run in order and add into
 // fp32 accumulators (a (token, head) belongs to one sparse row per branch: plain read-add-write, no atomics),
 // which grad_store_kernel rounds once.
+//
+// A third addressing (VarArgs) runs the same kernels over slides packed token-major in one qkv buffer
+// (gp_dilated_attn_bwd_varlen): a work item of a branch is (slide, segment, head, 128-row tile), decoded through a
+// per-branch table of one VarEntry per slide in device memory -- the slide by a search of the wave-uniform prefix of
+// item counts, its entry by scalar loads.  Each slide keeps the geometry of its own length: nk / nq / npad come from
+// L_i, never from the packed row count, so the row after a slide's last token (the next slide's CLS) is a tail row
+// like any other.  Everything after make_view is the source the other two instantiations compile.
 #include <math.h>
+
+#include <cstring>
 
 #include <type_traits>
 
@@ -94,6 +103,30 @@ struct DilArgs {
   float c, c_log2;               // factor of dq / dk; factor of q.k in the log2-domain logit
 };
 
+// One slide of one branch of gp_dilated_attn_bwd_varlen (device table, [nbranch][nslide]).
+struct VarEntry {
+  GpBranch g;                    // the branch's geometry for this slide's L
+  int32_t ntile;                 // ceil(g.m / kOwn)
+  int32_t item_begin;            // exclusive prefix of nseg * H * ntile over the branch's slides
+  int64_t L;                     // the slide's length (CLS + tiles)
+  int64_t tok0;                  // its first packed row (tok_off)
+  int64_t o_off, lse_off;        // elements: its region in the branch's packed o / dout and lse / delta buffers
+};
+static_assert(sizeof(VarEntry) == 64, "VarEntry is read as 16 words");
+
+// One branch of gp_dilated_attn_bwd_varlen: the packed q / k / v rows and the branch's packed buffers.
+struct VarArgs {
+  const uint16_t *q, *k, *v;     // [T, row_stride], head h at columns h*D
+  const uint16_t *o, *dout;      // slide-major regions [nseg_i, m_i, H, D]
+  const float* lse;              // slide-major regions [nseg_i, H, m_i]
+  float* delta;
+  float *gq, *gk, *gv;           // fp32 accumulators [T, H*D]
+  int64_t row_stride;
+  const VarEntry* tab;           // this branch's nslide entries
+  int32_t nslide, H;
+  float c, c_log2;
+};
+
 // What one work item (a (batch, head) of the seam, a (segment, head) of a dilated branch) addresses.
 struct View {
   const uint16_t *q, *k, *v, *dout, *o;
@@ -106,8 +139,11 @@ struct View {
   int npad;                      // zero-pad keys in the saved LSE (score 0, v = 0): m - nk; the seam has none
 };
 
+// make_view: the item's View; returns its 128-row tile.
 template <int D>
-GP_DEV void make_view(const BwdArgs& a, int64_t bh, View& w) {
+GP_DEV int make_view(const BwdArgs& a, int64_t item, View& w) {
+  const int tile = (int)(item % a.ntile);
+  const int64_t bh = item / a.ntile;
   const int b = (int)(bh / a.H), h = (int)(bh % a.H);
   const int64_t base = ((int64_t)b * a.L * a.H + h) * D;
   w.q = a.q + base; w.k = a.k + base; w.v = a.v + base; w.dout = a.dout + base; w.o = a.o + base;
@@ -119,19 +155,22 @@ GP_DEV void make_view(const BwdArgs& a, int64_t bh, View& w) {
   w.grs = 0;
   w.nk = w.nq = a.L;
   w.npad = 0;
+  return tile;
 }
-template <int D>
-GP_DEV void make_view(const DilArgs& a, int64_t bh, View& w) {
-  const GpBranch& g = a.g;
-  const int bn = (int)(bh / a.H), h = (int)(bh % a.H);
-  const int bidx = bn / g.nseg, n = bn % g.nseg, j = h / g.hpg;
-  const int64_t tok0 = (int64_t)bidx * a.L + (int64_t)n * g.s + j;      // the token of sparse row 0
+// Segment n, head h of a sequence of L tokens whose token 0 is packed row row0 and whose o / dout and lse / delta
+// regions start at obase / sbase (elements) of the branch's buffers.  L is the sequence's own length: every row
+// limit below is taken against it.
+template <int D, class A>
+GP_DEV void dil_view(const A& a, const GpBranch& g, int64_t L, int64_t row0, int64_t obase, int64_t sbase, int n, int h,
+                     View& w) {
+  const int j = h / g.hpg;
+  const int64_t tok0 = row0 + (int64_t)n * g.s + j;                      // the token of sparse row 0
   const int64_t off = tok0 * a.row_stride + h * D;
   w.q = a.q + off; w.k = a.k + off; w.v = a.v + off;
-  const int64_t ooff = ((int64_t)bn * g.m * a.H + h) * D;
+  const int64_t ooff = obase + ((int64_t)n * g.m * a.H + h) * D;
   w.dout = a.dout + ooff;
   w.o = a.o + ooff;
-  const int64_t soff = ((int64_t)bn * a.H + h) * g.m;
+  const int64_t soff = sbase + ((int64_t)n * a.H + h) * g.m;
   w.lse = a.lse + soff;
   w.delta = a.delta + soff;
   w.dq = w.dk = w.dv = nullptr;
@@ -140,11 +179,57 @@ GP_DEV void make_view(const DilArgs& a, int64_t bh, View& w) {
   w.rs = a.row_stride * g.r;
   w.rso = (int64_t)a.H * D;
   w.grs = (int64_t)a.H * D * g.r;
-  w.nk = gp_valid_rows(g, a.L, n, j);
-  const int64_t lim = a.L - ((int64_t)n * g.g + j);                      // merge slots n g + i r + j < L
+  w.nk = gp_valid_rows(g, L, n, j);
+  const int64_t lim = L - ((int64_t)n * g.g + j);                        // merge slots n g + i r + j < L
   const int64_t nq = lim > 0 ? (lim + g.r - 1) / g.r : 0;
   w.nq = (int)(nq < g.m ? nq : g.m);
   w.npad = g.m - w.nk;
+}
+template <int D>
+GP_DEV int make_view(const DilArgs& a, int64_t item, View& w) {
+  const GpBranch& g = a.g;
+  const int tile = (int)(item % a.ntile);
+  const int64_t bh = item / a.ntile;
+  const int bn = (int)(bh / a.H), h = (int)(bh % a.H);
+  const int bidx = bn / g.nseg, n = bn % g.nseg;
+  const int64_t seg0 = (int64_t)bidx * g.nseg;
+  dil_view<D>(a, g, a.L, (int64_t)bidx * a.L, seg0 * g.m * a.H * D, seg0 * a.H * g.m, n, h, w);
+  return tile;
+}
+
+// A table entry by scalar loads (wave-uniform address, constant address space) instead of flat loads into VGPRs,
+// as the forward's varlen decode does.
+GP_DEV void load_entry_scalar(const VarEntry* src_entry, VarEntry& e) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  uint32_t words[sizeof(VarEntry) / 4];
+  const __attribute__((address_space(4))) uint32_t* src =
+      (const __attribute__((address_space(4))) uint32_t*)(uintptr_t)src_entry;
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(VarEntry) / 4); ++i) words[i] = src[i];
+  __builtin_memcpy(&e, words, sizeof(VarEntry));
+#else
+  e = *src_entry;
+#endif
+}
+// Packed slides: the slide is the last entry whose item_begin <= item (every slide has items: L_i >= 1), then
+// (segment, head, tile) within it.  item derives from blockIdx alone, so the search and the entry are wave-uniform.
+template <int D>
+GP_DEV int make_view(const VarArgs& a, int64_t item, View& w) {
+  const int it = (int)item;
+  int lo = 0, hi = a.nslide - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (it >= a.tab[mid].item_begin) lo = mid; else hi = mid - 1;
+  }
+  lo = __builtin_amdgcn_readfirstlane(lo);
+  VarEntry e;
+  load_entry_scalar(a.tab + lo, e);
+  const int local = it - e.item_begin;
+  const int tile = local % e.ntile;
+  const int nh = local / e.ntile;
+  const int n = nh / a.H, h = nh % a.H;
+  dil_view<D>(a, e.g, e.L, e.tok0, e.o_off, e.lse_off, n, h, w);
+  return tile;
 }
 
 GP_DEV void add_f32x4(float* p, f32x4 v, float c) {                      // read-add-write, 16-byte aligned
@@ -226,17 +311,16 @@ struct TileStage {
 
 // ---------------------------------------------------------------------------------------
 // dQ (and delta): one workgroup per 128 query rows of a (batch, head).
-template <int D, bool kH, bool kDil>
-__global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const std::conditional_t<kDil, DilArgs, BwdArgs> a) {
+template <int D, bool kH, class Args>
+__global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const Args a) {
+  constexpr bool kDil = !std::is_same_v<Args, BwdArgs>;     // the dilated addressings: DilArgs, VarArgs
   using TS = TileStage<D>;
   constexpr int DT = D / 16, ROWB = TS::ROWB, TILEB = TS::TILEB;
   __shared__ __attribute__((aligned(16))) char smem[4 * TILEB];   // [K0 | V0 | K1 | V1]
 
   const int64_t item = xcd_group(blockIdx.x, gridDim.x);
-  const int tile = (int)(item % a.ntile);
-  const int64_t bh = item / a.ntile;
   View vw;
-  make_view<D>(a, bh, vw);
+  const int tile = make_view<D>(a, item, vw);
   const int L = vw.nk;                               // keys; the seam's seqlen
   const int nst = vw.nk < vw.nq ? vw.nk : vw.nq;     // rows whose dq is stored
   if constexpr (kDil)
@@ -394,18 +478,17 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const std::conditional
 
 // ---------------------------------------------------------------------------------------
 // dK / dV: one workgroup per 128 keys of a (batch, head).
-template <int D, bool kH, bool kDil>
-__global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const std::conditional_t<kDil, DilArgs, BwdArgs> a) {
+template <int D, bool kH, class Args>
+__global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const Args a) {
+  constexpr bool kDil = !std::is_same_v<Args, BwdArgs>;     // the dilated addressings: DilArgs, VarArgs
   using TS = TileStage<D>;
   constexpr int DT = D / 16, ROWB = TS::ROWB, TILEB = TS::TILEB;
   constexpr int STATB = 2 * kTile * 4;                            // lse * log2(e) | delta of a query tile
   __shared__ __attribute__((aligned(16))) char smem[4 * TILEB + 2 * STATB];   // [Q0 | dO0 | Q1 | dO1 | stat0 | stat1]
 
   const int64_t item = xcd_group(blockIdx.x, gridDim.x);
-  const int tile = (int)(item % a.ntile);
-  const int64_t bh = item / a.ntile;
   View vw;
-  make_view<D>(a, bh, vw);
+  const int tile = make_view<D>(a, item, vw);
   const int L = vw.nq;                               // query rows that carry a dout; the seam's seqlen
   const int nkey = vw.nk;
   if constexpr (kDil)
@@ -540,8 +623,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const std::conditiona
 
 template <int D, bool kH>
 void launch_bwd(const BwdArgs& a, unsigned grid, hipStream_t s) {
-  attn_bwd_dq_kernel<D, kH, false><<<grid, 256, 0, s>>>(a);
-  attn_bwd_dkv_kernel<D, kH, false><<<grid, 256, 0, s>>>(a);
+  attn_bwd_dq_kernel<D, kH, BwdArgs><<<grid, 256, 0, s>>>(a);
+  attn_bwd_dkv_kernel<D, kH, BwdArgs><<<grid, 256, 0, s>>>(a);
 }
 
 bool bwd_dim_ok(int D) { return D == 48 || D == 64 || D == 96; }
@@ -562,28 +645,28 @@ struct MergeBwdArgs {
   int32_t H, nbranch;
 };
 
-template <int D, bool kH>
-__global__ __launch_bounds__(256) void merge_bwd_kernel(const MergeBwdArgs a) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= a.B * a.L * a.H) return;
-  const int h = (int)(idx % a.H);
-  const int64_t tok = idx / a.H;
-  const int bidx = (int)(tok / a.L), p = (int)(tok % a.L);
+// Token p, head h of one sequence (a batch element, or a packed slide).  region(b, g, lse, dout) gives branch b's
+// geometry for that sequence and the bases of the sequence's regions in the branch's lse and dout buffers; dm is the
+// (token, head)'s D elements of dmerged.
+template <int D, bool kH, class F>
+GP_DEV void merge_bwd_token(int nbranch, int H, int p, int h, const uint16_t* dm, F region) {
   float e[GP_MAX_BRANCHES];
-  int64_t row[GP_MAX_BRANCHES];                          // of dout (rows of D)
+  uint16_t* drows[GP_MAX_BRANCHES];                      // the dout row (D elements)
   bool cov[GP_MAX_BRANCHES];
   float mx = -INFINITY;
 #pragma unroll
   for (int b = 0; b < GP_MAX_BRANCHES; ++b) {
-    e[b] = -1e8f; cov[b] = false; row[b] = 0;
-    if (b < a.nbranch) {
-      const GpBranch g = a.g[b];
+    e[b] = -1e8f; cov[b] = false; drows[b] = nullptr;
+    if (b < nbranch) {
+      GpBranch g;
+      const float* lse;
+      uint16_t* dout;
+      region(b, g, lse, dout);
       const int n = p / g.g, pt = p - n * g.g;
       const int i = pt / g.r, j = pt - i * g.r;
-      const int64_t bn = (int64_t)bidx * g.nseg + n;
       cov[b] = h / g.hpg == j;
-      row[b] = (bn * g.m + i) * a.H + h;
-      if (cov[b]) e[b] = a.lse[b][(bn * a.H + h) * g.m + i];
+      drows[b] = dout + (((int64_t)n * g.m + i) * H + h) * D;
+      if (cov[b]) e[b] = lse[((int64_t)n * H + h) * g.m + i];
       if (!cov[b] || e[b] == 0.f) e[b] = -1e8f;            // dilated_attention.py:46
       mx = fmaxf(mx, e[b]);
     }
@@ -591,17 +674,16 @@ __global__ __launch_bounds__(256) void merge_bwd_kernel(const MergeBwdArgs a) {
   float wsum = 0.f;
 #pragma unroll
   for (int b = 0; b < GP_MAX_BRANCHES; ++b)
-    if (b < a.nbranch) {
+    if (b < nbranch) {
       e[b] = __builtin_amdgcn_exp2f((e[b] - mx) * kLog2e);
       wsum += e[b];
     }
   const float inv = __builtin_amdgcn_rcpf(wsum);
-  const uint16_t* dm = a.dmerged + (tok * a.H + h) * D;
 #pragma unroll
   for (int b = 0; b < GP_MAX_BRANCHES; ++b)
-    if (b < a.nbranch && cov[b]) {
+    if (b < nbranch && cov[b]) {
       const float wb = e[b] * inv;
-      uint16_t* drow = a.dout[b] + row[b] * D;
+      uint16_t* drow = drows[b];
 #pragma unroll
       for (int c = 0; c < D; c += 8) {
         float x[8];
@@ -610,6 +692,54 @@ __global__ __launch_bounds__(256) void merge_bwd_kernel(const MergeBwdArgs a) {
                                                          pack2e<kH>(x[4] * wb, x[5] * wb), pack2e<kH>(x[6] * wb, x[7] * wb));
       }
     }
+}
+
+template <int D, bool kH>
+__global__ __launch_bounds__(256) void merge_bwd_kernel(const MergeBwdArgs a) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= a.B * a.L * a.H) return;
+  const int h = (int)(idx % a.H);
+  const int64_t tok = idx / a.H;
+  const int bidx = (int)(tok / a.L), p = (int)(tok % a.L);
+  merge_bwd_token<D, kH>(a.nbranch, a.H, p, h, a.dmerged + (tok * a.H + h) * D,
+                         [&](int b, GpBranch& g, const float*& lse, uint16_t*& dout) {
+                           g = a.g[b];
+                           const int64_t seg0 = (int64_t)bidx * g.nseg;
+                           lse = a.lse[b] + seg0 * a.H * g.m;
+                           dout = a.dout[b] + seg0 * g.m * a.H * D;
+                         });
+}
+
+// The merge backward of packed slides: one thread per (packed token, head); the slide is the last one whose first
+// row tok0 <= token (branch 0's entries), the geometry and the region bases come from the (branch, slide) entries.
+struct VarMergeArgs {
+  const float* lse[GP_MAX_BRANCHES];
+  uint16_t* dout[GP_MAX_BRANCHES];
+  const VarEntry* tab;           // [nbranch][nslide]
+  const uint16_t* dmerged;       // [T, H*D]
+  int64_t T;
+  int32_t nslide, H, nbranch;
+};
+
+template <int D, bool kH>
+__global__ __launch_bounds__(256) void merge_bwd_varlen_kernel(const VarMergeArgs a) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= a.T * a.H) return;
+  const int h = (int)(idx % a.H);
+  const int64_t tok = idx / a.H;
+  int lo = 0, hi = a.nslide - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tok >= a.tab[mid].tok0) lo = mid; else hi = mid - 1;
+  }
+  const int p = (int)(tok - a.tab[lo].tok0);
+  merge_bwd_token<D, kH>(a.nbranch, a.H, p, h, a.dmerged + (tok * a.H + h) * D,
+                         [&](int b, GpBranch& g, const float*& lse, uint16_t*& dout) {
+                           const VarEntry& e = a.tab[(int64_t)b * a.nslide + lo];
+                           g = e.g;
+                           lse = a.lse[b] + e.lse_off;
+                           dout = a.dout[b] + e.o_off;
+                         });
 }
 
 // The one rounding of the accumulated gradients: g [rows, 3, E] fp32 planes -> dq / dk / dv rows (stride ds).
@@ -673,12 +803,65 @@ void launch_dil_bwd(const MergeBwdArgs& m, DilArgs a, const DilWs& w, char* ws, 
     a.delta = reinterpret_cast<float*>(ws + w.delta[b]);
     a.ntile = (a.g.m + kOwn - 1) / kOwn;
     const unsigned grid = (unsigned)(B * a.g.nseg * m.H * a.ntile);
-    attn_bwd_dq_kernel<D, kH, true><<<grid, 256, 0, s>>>(a);
-    attn_bwd_dkv_kernel<D, kH, true><<<grid, 256, 0, s>>>(a);
+    attn_bwd_dq_kernel<D, kH, DilArgs><<<grid, 256, 0, s>>>(a);
+    attn_bwd_dkv_kernel<D, kH, DilArgs><<<grid, 256, 0, s>>>(a);
   }
   const int E = m.H * D;
   const int64_t n4 = B * m.L * (E / 4);
   grad_store_kernel<kH><<<(unsigned)((n4 + 255) / 256), 256, 0, s>>>(a.gq, a.gk, a.gv, dq, dk, dv, ds, B * m.L, E);
+}
+
+// gp_varlen_bwd_plan's buffer: this header (host side only), then the [nbranch][nslide] VarEntry table the kernels
+// read from the device copy.  Its first fields, up to items, are public (include/gigapath_hip.h).
+constexpr int32_t kVarBwdMagic = 0x47504231;   // "GPB1"
+struct VarBwdHdr {
+  int32_t magic, nslide, nbranch, H, D, reserved;
+  int64_t T;
+  int64_t items[GP_MAX_BRANCHES];              // work items of each branch's two attention launches
+  int64_t qkv_stride;
+  const uint16_t* qkv;
+  const uint16_t* o[GP_MAX_BRANCHES];
+  const float* lse[GP_MAX_BRANCHES];
+  int64_t ws_dout[GP_MAX_BRANCHES], ws_delta[GP_MAX_BRANCHES], ws_g[3], ws_total;
+  int64_t tab_off, bytes;
+};
+inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+void var_bwd_layout(int nslide, int nbranch, VarBwdHdr& h) {
+  h.tab_off = align_up((int64_t)sizeof(VarBwdHdr), 16);
+  h.bytes = align_up(h.tab_off + (int64_t)nslide * nbranch * (int64_t)sizeof(VarEntry), 16);
+}
+
+template <int D, bool kH>
+void launch_var_bwd(const VarBwdHdr& h, const VarEntry* tab, char* ws, const uint16_t* dmerged, float c, float c_log2,
+                    uint16_t* dq, uint16_t* dk, uint16_t* dv, int64_t ds, hipStream_t s) {
+  const int E = h.H * D;
+  VarMergeArgs m = {};
+  for (int b = 0; b < h.nbranch; ++b) {
+    m.lse[b] = h.lse[b];
+    m.dout[b] = reinterpret_cast<uint16_t*>(ws + h.ws_dout[b]);
+  }
+  m.tab = tab; m.dmerged = dmerged; m.T = h.T;
+  m.nslide = h.nslide; m.H = h.H; m.nbranch = h.nbranch;
+  merge_bwd_varlen_kernel<D, kH><<<(unsigned)((h.T * h.H + 255) / 256), 256, 0, s>>>(m);
+  VarArgs a = {};
+  a.q = h.qkv; a.k = h.qkv + E; a.v = h.qkv + 2 * E;
+  a.gq = reinterpret_cast<float*>(ws + h.ws_g[0]);
+  a.gk = reinterpret_cast<float*>(ws + h.ws_g[1]);
+  a.gv = reinterpret_cast<float*>(ws + h.ws_g[2]);
+  a.row_stride = h.qkv_stride; a.nslide = h.nslide; a.H = h.H;
+  a.c = c; a.c_log2 = c_log2;
+  for (int b = 0; b < h.nbranch; ++b) {                    // fixed order: each branch adds into the accumulators
+    a.o = h.o[b];
+    a.dout = m.dout[b];
+    a.lse = h.lse[b];
+    a.delta = reinterpret_cast<float*>(ws + h.ws_delta[b]);
+    a.tab = tab + (int64_t)b * h.nslide;
+    const unsigned grid = (unsigned)h.items[b];
+    attn_bwd_dq_kernel<D, kH, VarArgs><<<grid, 256, 0, s>>>(a);
+    attn_bwd_dkv_kernel<D, kH, VarArgs><<<grid, 256, 0, s>>>(a);
+  }
+  const int64_t n4 = h.T * (E / 4);
+  grad_store_kernel<kH><<<(unsigned)((n4 + 255) / 256), 256, 0, s>>>(a.gq, a.gk, a.gv, dq, dk, dv, ds, h.T, E);
 }
 
 }  // namespace
@@ -819,4 +1002,157 @@ extern "C" int gp_dilated_attn_bwd(const uint16_t* q, const uint16_t* k, const u
     default: if (kh) launch_dil_bwd<96, true>(m, a, w, ws, o_in, B, dq, dk, dv, d_row_stride, s); else launch_dil_bwd<96, false>(m, a, w, ws, o_in, B, dq, dk, dv, d_row_stride, s); break;
   }
   return gp_check_launch("gp_dilated_attn_bwd");
+}
+
+// ---------------------------------------------------------------------------------------
+// Packed slides (varlen): the plan holds the host header and the device table; the launch call copies nothing.
+extern "C" int64_t gp_varlen_bwd_plan_bytes(int nslide, int nbranch) {
+  if (nslide < 1 || nbranch < 1 || nbranch > GP_MAX_BRANCHES) return -1;
+  VarBwdHdr h;
+  var_bwd_layout(nslide, nbranch, h);
+  return h.bytes;
+}
+
+extern "C" int gp_varlen_bwd_plan(const int64_t* L, int nslide, int H, int D, const int32_t* seg_len,
+                                  const int32_t* ratios, int nbranch, const uint16_t* qkv, int64_t qkv_row_stride,
+                                  const uint16_t* const* o_in, const float* const* lse_in, void* plan_host,
+                                  int64_t plan_bytes, int64_t* workspace_bytes) {
+  GP_REQUIRE(L && seg_len && ratios && workspace_bytes, "gp_varlen_bwd_plan: null pointer (%s)",
+             !L ? "L" : !seg_len ? "seg_len" : !ratios ? "ratios" : "workspace_bytes");
+  GP_REQUIRE(nslide >= 1, "gp_varlen_bwd_plan: nslide must be >= 1 (got %d)", nslide);
+  GP_REQUIRE(nbranch >= 1 && nbranch <= GP_MAX_BRANCHES, "gp_varlen_bwd_plan: nbranch must be 1..%d (got %d)",
+             GP_MAX_BRANCHES, nbranch);
+  GP_REQUIRE(D == 48, "gp_varlen_bwd_plan: head dim %d unsupported (the varlen kernels cover D = 48)", D);
+  GP_REQUIRE(H > 0 && H <= 4096, "gp_varlen_bwd_plan: bad H %d", H);
+  const int64_t E = (int64_t)H * D;
+  GP_REQUIRE(qkv_row_stride >= 3 * E && qkv_row_stride % 8 == 0,
+             "gp_varlen_bwd_plan: qkv_row_stride %lld below 3*H*D = %lld or not a multiple of 8",
+             (long long)qkv_row_stride, (long long)(3 * E));
+  int64_t T = 0;
+  for (int i = 0; i < nslide; ++i) {
+    GP_REQUIRE(L[i] > 0 && L[i] < (int64_t)0x7fffffff, "gp_varlen_bwd_plan: slide %d has L = %lld", i, (long long)L[i]);
+    T += L[i];
+    GP_REQUIRE(T < (int64_t)0x7fffffff, "gp_varlen_bwd_plan: %lld packed tokens exceed 2^31 - 1", (long long)T);
+  }
+  GP_REQUIRE((T * H + 255) / 256 < (int64_t)0x7fffffff && (T * (E / 4) + 255) / 256 < (int64_t)0x7fffffff,
+             "gp_varlen_bwd_plan: T*H*D too large for one launch");
+  VarBwdHdr h;
+  memset(&h, 0, sizeof(h));
+  var_bwd_layout(nslide, nbranch, h);
+  uint64_t off = 0;
+  auto take = [&](uint64_t bytes) {
+    const uint64_t at = off;
+    off += (bytes + 255) / 256 * 256;
+    return (int64_t)at;
+  };
+  for (int b = 0; b < nbranch; ++b) {
+    GP_REQUIRE(seg_len[b] > 0 && ratios[b] > 0, "gp_varlen_bwd_plan: branch %d: bad seg_len %d / ratio %d", b, seg_len[b],
+               ratios[b]);
+    uint64_t rows = 0;                                      // (sparse row, head)s of every slide
+    int64_t items = 0;
+    for (int i = 0; i < nslide; ++i) {
+      const GpBranch g = gp_make_branch(L[i], seg_len[b], ratios[b], H);
+      rows += (uint64_t)g.nseg * g.m * H;
+      items += (int64_t)g.nseg * H * ((g.m + kOwn - 1) / kOwn);
+      GP_REQUIRE(items < (int64_t)0x7fffffff, "gp_varlen_bwd_plan: branch %d: %lld work items exceed one launch", b,
+                 (long long)items);
+    }
+    h.items[b] = items;
+    h.ws_dout[b] = take(rows * D * sizeof(uint16_t));
+    h.ws_delta[b] = take(rows * sizeof(float));
+  }
+  for (int i = 0; i < 3; ++i) h.ws_g[i] = take((uint64_t)T * E * sizeof(float));
+  h.ws_total = (int64_t)off;
+  *workspace_bytes = h.ws_total;
+  if (plan_host == nullptr) return 0;                       // sizing call
+
+  GP_REQUIRE(plan_bytes >= h.bytes, "gp_varlen_bwd_plan: plan buffer %lld < %lld bytes (gp_varlen_bwd_plan_bytes)",
+             (long long)plan_bytes, (long long)h.bytes);
+  GP_REQUIRE(gp_aligned(plan_host, 8), "gp_varlen_bwd_plan: misaligned pointer (plan_host, 8 bytes)");
+  GP_REQUIRE(qkv != nullptr && o_in != nullptr && lse_in != nullptr, "gp_varlen_bwd_plan: null pointer (%s)",
+             !qkv ? "qkv" : !o_in ? "o_in" : "lse_in");
+  GP_REQUIRE(gp_aligned(qkv, 16), "gp_varlen_bwd_plan: misaligned pointer (qkv)");
+  for (int b = 0; b < nbranch; ++b) {
+    GP_REQUIRE(o_in[b] != nullptr && lse_in[b] != nullptr, "gp_varlen_bwd_plan: null pointer (o_in / lse_in [%d])", b);
+    GP_REQUIRE(gp_aligned(o_in[b], 16) && gp_aligned(lse_in[b], 4),
+               "gp_varlen_bwd_plan: misaligned pointer (o_in / lse_in [%d])", b);
+  }
+  char* base = static_cast<char*>(plan_host);
+  memset(base, 0, (size_t)h.bytes);
+  VarEntry* tab = reinterpret_cast<VarEntry*>(base + h.tab_off);
+  for (int b = 0; b < nbranch; ++b) {
+    int64_t tok = 0, oo = 0, lo = 0, items = 0;
+    for (int i = 0; i < nslide; ++i) {
+      VarEntry& e = tab[(size_t)b * nslide + i];
+      e.g = gp_make_branch(L[i], seg_len[b], ratios[b], H);
+      e.ntile = (e.g.m + kOwn - 1) / kOwn;
+      e.item_begin = (int32_t)items;
+      e.L = L[i];
+      e.tok0 = tok;
+      e.o_off = oo;
+      e.lse_off = lo;
+      items += (int64_t)e.g.nseg * H * e.ntile;
+      tok += L[i];
+      oo += (int64_t)e.g.nseg * e.g.m * H * D;
+      lo += (int64_t)e.g.nseg * H * e.g.m;
+    }
+    h.o[b] = o_in[b];
+    h.lse[b] = lse_in[b];
+  }
+  h.magic = kVarBwdMagic;
+  h.nslide = nslide; h.nbranch = nbranch; h.H = H; h.D = D;
+  h.T = T;
+  h.qkv_stride = qkv_row_stride;
+  h.qkv = qkv;
+  memcpy(base, &h, sizeof(h));
+  return 0;
+}
+
+extern "C" int gp_dilated_attn_bwd_varlen(const void* plan_host, const void* plan_dev, const uint16_t* dmerged,
+                                          uint16_t* dq, uint16_t* dk, uint16_t* dv, int64_t d_row_stride,
+                                          void* workspace, size_t workspace_bytes, int fmt, void* stream) {
+  GP_REQUIRE(fmt == GP_FMT_BF16 || fmt == GP_FMT_F16,
+             "gp_dilated_attn_bwd_varlen: bad fmt %d (GP_FMT_BF16 or GP_FMT_F16)", fmt);
+  GP_REQUIRE(plan_host != nullptr && plan_dev != nullptr, "gp_dilated_attn_bwd_varlen: null pointer (%s)",
+             !plan_host ? "plan_host" : "plan_dev");
+  GP_REQUIRE(gp_aligned(plan_host, 8) && gp_aligned(plan_dev, 16),
+             "gp_dilated_attn_bwd_varlen: misaligned pointer (plan_host 8 bytes / plan_dev 16 bytes)");
+  VarBwdHdr h;
+  memcpy(&h, plan_host, sizeof(h));
+  GP_REQUIRE(h.magic == kVarBwdMagic, "gp_dilated_attn_bwd_varlen: not a gp_varlen_bwd_plan buffer");
+  GP_REQUIRE(h.D == 48 && h.nslide >= 1 && h.nbranch >= 1 && h.nbranch <= GP_MAX_BRANCHES && h.H > 0 && h.T > 0 &&
+                 h.T < (int64_t)0x7fffffff,
+             "gp_dilated_attn_bwd_varlen: corrupt plan header");
+  const void* ptrs[] = {dmerged, dq, dk, dv};
+  const char* names[] = {"dmerged", "dq", "dk", "dv"};
+  for (int i = 0; i < 4; ++i) {
+    GP_REQUIRE(ptrs[i] != nullptr, "gp_dilated_attn_bwd_varlen: null pointer (%s)", names[i]);
+    GP_REQUIRE(gp_aligned(ptrs[i], 16), "gp_dilated_attn_bwd_varlen: misaligned pointer (%s)", names[i]);
+  }
+  const int64_t E = (int64_t)h.H * h.D;
+  GP_REQUIRE(d_row_stride >= E && d_row_stride % 8 == 0,
+             "gp_dilated_attn_bwd_varlen: d_row_stride %lld below H*D = %lld or not a multiple of 8",
+             (long long)d_row_stride, (long long)E);
+  GP_REQUIRE(workspace != nullptr && workspace_bytes >= (size_t)h.ws_total,
+             "gp_dilated_attn_bwd_varlen: workspace too small (%zu bytes, gp_varlen_bwd_plan asks %zu)",
+             workspace ? workspace_bytes : (size_t)0, (size_t)h.ws_total);
+  GP_REQUIRE(gp_aligned(workspace, 16), "gp_dilated_attn_bwd_varlen: misaligned workspace (16 bytes)");
+  for (int b = 0; b < h.nbranch; ++b)
+    GP_REQUIRE(h.items[b] > 0 && h.items[b] < (int64_t)0x7fffffff,
+               "gp_dilated_attn_bwd_varlen: branch %d: %lld work items exceed one launch", b, (long long)h.items[b]);
+
+  char* ws = static_cast<char*>(workspace);
+  const VarEntry* tab = reinterpret_cast<const VarEntry*>(static_cast<const char*>(plan_dev) + h.tab_off);
+  hipStream_t s = gp_stream(stream);
+  // the accumulators start at zero: a (token, head) no branch covers keeps it
+  const hipError_t me = hipMemsetAsync(ws + h.ws_g[0], 0, (size_t)(h.ws_total - h.ws_g[0]), s);
+  if (me != hipSuccess) {
+    gp_set_error("gp_dilated_attn_bwd_varlen: hipMemsetAsync: %s", hipGetErrorString(me));
+    return (int)me;
+  }
+  // the forward's q is pre-scaled (logits q'.k in the log2 domain): dq' = ln 2 dS k, dk = ln 2 dS^T q'
+  const float c = 0.6931471805599453f, c_log2 = 1.f;
+  if (fmt == GP_FMT_F16) launch_var_bwd<48, true>(h, tab, ws, dmerged, c, c_log2, dq, dk, dv, d_row_stride, s);
+  else launch_var_bwd<48, false>(h, tab, ws, dmerged, c, c_log2, dq, dk, dv, d_row_stride, s);
+  return gp_check_launch("gp_dilated_attn_bwd_varlen");
 }

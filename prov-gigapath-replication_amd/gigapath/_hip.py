@@ -94,6 +94,9 @@ SIGNATURES = {
     "gp_varlen_plan": [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp],
     "gp_dilated_attn_fwd_varlen": [c_vp, c_vp, c_i32, c_i32, c_vp],
     "gp_branch_merge_ln_varlen": [c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_i32, c_vp],
+    "gp_varlen_bwd_plan_bytes": [c_i32, c_i32],
+    "gp_varlen_bwd_plan": [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp],
+    "gp_dilated_attn_bwd_varlen": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, ctypes.c_size_t, c_i32, c_vp],
     "gp_gemm_workspace_bytes": [c_i64, c_i64, c_i64],
     "gp_linear": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_i32, c_vp],
     "gp_ffn_fc1_gelu": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i32, c_vp],
@@ -109,6 +112,7 @@ SIGNATURES = {
                             c_vp, c_f32, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i32, c_vp],
 }
 _RESTYPES = {"gp_last_error_string": ctypes.c_char_p, "gp_varlen_plan_bytes": c_i64, "gp_gemm_workspace_bytes": c_i64,
+             "gp_varlen_bwd_plan_bytes": c_i64,
              "gp_cls_attn_workspace_bytes": c_i64, "gp_attn_rows_plan_bytes": c_i64,
              "gp_seg_attn_bwd_workspace_bytes": ctypes.c_size_t,
              "gp_dilated_attn_bwd_workspace_bytes": ctypes.c_size_t,
@@ -778,6 +782,83 @@ def branch_merge_ln_varlen(plan: VarlenPlan, ln_w, ln_b, eps, out):
         raise TypeError("branch_merge_ln_varlen: out must be in the plan's 16-bit format")
     _check(lib.gp_branch_merge_ln_varlen(plan.host, _ptr(plan.dev), _ptr(ln_w), _ptr(ln_b), eps, _ptr(out),
                                          plan.fmt, _stream()), "gp_branch_merge_ln_varlen")
+
+
+class VarlenBwdHdr(ctypes.Structure):
+    """The public head of a gp_varlen_bwd_plan buffer (include/gigapath_hip.h)."""
+    _fields_ = [("magic", c_i32), ("nslide", c_i32), ("nbranch", c_i32), ("H", c_i32), ("D", c_i32),
+                ("reserved", c_i32), ("T", c_i64), ("items", c_i64 * MAX_BRANCHES)]
+
+
+class VarlenBwdPlan:
+    """Work table of dilated_attn_bwd_varlen for `Ls` slides packed token-major in one [T, 3E] qkv buffer.
+
+    ``VarlenBwdPlan(Ls, H, D, segs, ratios)`` sizes the workspace (``workspace_bytes``) and the plan (``nbytes``);
+    ``bind(qkv, outs, lses)`` writes the table for the forward's packed per-branch outputs (VarlenPlan's layouts)
+    and copies it to the device; ``items`` are then the per-branch work-item counts.  The tensors are kept alive
+    with the plan."""
+
+    def __init__(self, Ls: Sequence[int], H: int, D: int, segs: Sequence[int], ratios: Sequence[int]):
+        lib = load_library()
+        self.Ls = [int(x) for x in Ls]
+        self.H, self.D, self.segs, self.ratios = H, D, list(segs), list(ratios)
+        self._L = (c_i64 * len(self.Ls))(*self.Ls)
+        ws = c_i64()
+        _check(lib.gp_varlen_bwd_plan(self._L, len(self.Ls), H, D, _i32_array(self.segs), _i32_array(self.ratios),
+                                      len(self.segs), None, 3 * H * D, None, None, None, 0, ctypes.byref(ws)),
+               "gp_varlen_bwd_plan")
+        self.workspace_bytes = int(ws.value)
+        self.nbytes = int(lib.gp_varlen_bwd_plan_bytes(len(self.Ls), len(self.segs)))
+        self.T = sum(self.Ls)
+        self.host = None
+        self.dev = None
+        self.items = None
+
+    def bind(self, qkv: torch.Tensor, outs: Sequence[torch.Tensor], lses: Sequence[torch.Tensor]):
+        lib = load_library()
+        self.fmt = fmt_of(qkv.dtype)
+        _dev(qkv, name="qkv")
+        if qkv.dim() != 2 or qkv.shape[0] < self.T or qkv.shape[1] != 3 * self.H * self.D:
+            raise ValueError("VarlenBwdPlan.bind: qkv must be [>= %d, %d]" % (self.T, 3 * self.H * self.D))
+        if len(outs) != len(self.segs) or len(lses) != len(self.segs):
+            raise ValueError("VarlenBwdPlan.bind: one o / lse buffer per branch")
+        sizes = VarlenPlan(self.Ls, self.H, self.D, self.segs, self.ratios)
+        for b, (o, l) in enumerate(zip(outs, lses)):
+            _dev(o, qkv.dtype, "o[%d]" % b); _dev(l, torch.float32, "lse[%d]" % b)
+            if o.numel() < sizes.o_elems[b] or l.numel() < sizes.lse_elems[b]:
+                raise ValueError("VarlenBwdPlan.bind: branch %d buffers too small" % b)
+        host = (ctypes.c_uint64 * ((self.nbytes + 7) // 8))()          # 8-byte aligned
+        ws = c_i64()
+        _check(lib.gp_varlen_bwd_plan(self._L, len(self.Ls), self.H, self.D, _i32_array(self.segs),
+                                      _i32_array(self.ratios), len(self.segs), _ptr(qkv), 3 * self.H * self.D,
+                                      _ptr_array(outs), _ptr_array(lses), host, self.nbytes, ctypes.byref(ws)),
+               "gp_varlen_bwd_plan")
+        self.host = host
+        self.items = list(VarlenBwdHdr.from_buffer(host).items)[:len(self.segs)]
+        self.dev = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(qkv.device)
+        self._keep = (qkv, list(outs), list(lses))
+        return self
+
+
+def dilated_attn_bwd_varlen(plan: VarlenBwdPlan, dmerged, dq, dk, dv, d_row_stride):
+    """Backward of dilated_attn_fwd_varlen + the no-LN branch_merge_ln_varlen (gp_dilated_attn_bwd_varlen) for the
+    qkv / outs / lses the plan is bound to: dmerged [T, H*D] contiguous; dq / dk / dv views whose rows are
+    d_row_stride elements apart (a fused [T, 3E] dqkv), all in qkv's 16-bit dtype."""
+    lib = load_library()
+    if plan.host is None:
+        raise RuntimeError("dilated_attn_bwd_varlen: the plan is not bound")
+    act = ACT_DTYPES[plan.fmt]
+    for nm, t in (("dq", dq), ("dk", dk), ("dv", dv)):
+        if not t.is_cuda or t.dtype != act:
+            raise TypeError("dilated_attn_bwd_varlen: %s must be a device tensor of qkv's 16-bit dtype" % nm)
+    _dev(dmerged, act, "dmerged")
+    if dmerged.numel() != plan.T * plan.H * plan.D:
+        raise ValueError("dilated_attn_bwd_varlen: dmerged holds %d elements, expected %d"
+                         % (dmerged.numel(), plan.T * plan.H * plan.D))
+    ws = _bwd_workspace(dmerged.device, max(plan.workspace_bytes, 256))
+    _check(lib.gp_dilated_attn_bwd_varlen(plan.host, _ptr(plan.dev), _ptr(dmerged), _ptr(dq), _ptr(dk), _ptr(dv),
+                                          d_row_stride, ws.data_ptr(), ws.numel(), plan.fmt, _stream()),
+           "gp_dilated_attn_bwd_varlen")
 
 
 # ------------------------------------------------------------------------------------------

@@ -75,6 +75,19 @@ class ClassificationHead(nn.Module):
         feats = feats.to(self.classifier[0].weight.dtype)
         return self.classifier(feats.reshape(-1, feats.size(-1)))
 
+    def forward_packed(self, slides) -> torch.Tensor:
+        """slides: [(images_i [N_i, D] or [1, N_i, D], coords_i [N_i, 2] or [1, N_i, 2]), ...] of any lengths ->
+        logits [S, n_classes], through LongNetViT.forward_packed: one packed encoder forward (and, with a trainable
+        encoder, one packed backward) for the whole mixed-length batch."""
+        if self.encoder_trainable:
+            embeds = self.slide_encoder.forward_packed(slides, all_layer_embed=True)
+        else:
+            with torch.no_grad():
+                embeds = self.slide_encoder.forward_packed(slides, all_layer_embed=True)
+        feats = torch.cat([torch.cat([e[i] for i in self.feat_layer], dim=-1) for e in embeds], dim=0)
+        feats = feats.to(self.classifier[0].weight.dtype)
+        return self.classifier(feats)
+
 
 def get_model(**kwargs):
     return ClassificationHead(**kwargs)

@@ -623,6 +623,51 @@ def dilated_attention_grad(qkv: torch.Tensor, B: int, L: int, H: int, D: int, se
                                        float(softmax_scale))
 
 
+class _DilatedAttentionVarlenGrad(torch.autograd.Function):
+    """_DilatedAttentionGrad for slides packed token-major in one [T, 3E] qkv: one varlen attention launch and one
+    varlen merge forward, one gp_dilated_attn_bwd_varlen call backward.  The packed per-branch o / lse
+    are allocated per call (a VarlenScratch bound to this qkv) and saved, as there."""
+
+    @staticmethod
+    def forward(ctx, qkv, Ls, H, D, segs, ratios):
+        qkv = qkv.contiguous()
+        scratch = VarlenScratch(qkv.device, Ls, H, D, segs, ratios, qkv)
+        merged = torch.empty(qkv.shape[0], H * D, dtype=qkv.dtype, device=qkv.device)
+        _hip.dilated_attn_fwd_varlen(scratch.plan, True)
+        _hip.branch_merge_ln_varlen(scratch.plan, None, None, 0.0, merged)
+        ctx.save_for_backward(qkv, *scratch.outs, *scratch.lses)
+        ctx.geom = (tuple(Ls), H, D, tuple(segs), tuple(ratios))
+        return merged
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        Ls, H, D, segs, ratios = ctx.geom
+        E = H * D
+        qkv, rest = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        outs, lses = list(rest[:len(segs)]), list(rest[len(segs):])
+        dout = dout.to(qkv.dtype).contiguous()
+        dqkv = torch.empty_like(qkv)
+        plan = _hip.VarlenBwdPlan(Ls, H, D, segs, ratios).bind(qkv, outs, lses)
+        _hip.dilated_attn_bwd_varlen(plan, dout, dqkv, dqkv[:, E:], dqkv[:, 2 * E:], 3 * E)
+        return (dqkv,) + (None,) * 5
+
+
+def dilated_attention_grad_varlen(qkv: torch.Tensor, Ls: Sequence[int], H: int, D: int, segs, ratios) -> torch.Tensor:
+    """qkv [T, 3E] 16-bit, the slides of lengths Ls packed token-major (q | k | v, q already times D^-0.5 log2 e)
+    -> merged [T, E]: every slide's own dilated_attention_grad (its own segment schedule, no attention across
+    slides), with a native backward to qkv.  D = 48, the arch the varlen kernels cover."""
+    Ls = [int(x) for x in Ls]
+    if D != 48:
+        raise ValueError("dilated_attention_grad_varlen: the varlen kernels cover D = 48 (got %d)" % D)
+    if not Ls or min(Ls) < 1:
+        raise ValueError("dilated_attention_grad_varlen: every slide needs at least one token, got %s" % (Ls,))
+    if qkv.dtype not in _hip.ACT_DTYPES or qkv.dim() != 2 or qkv.shape != (sum(Ls), 3 * H * D):
+        raise ValueError("dilated_attention_grad_varlen: qkv must be [sum(Ls), 3*H*D] bf16 or fp16, got %s %s"
+                         % (tuple(qkv.shape), qkv.dtype))
+    return _DilatedAttentionVarlenGrad.apply(qkv, Ls, H, D, list(segs), list(ratios))
+
+
 # The training FFN's middle: gelu + ffn_layernorm as gp_gelu_layernorm / gp_gelu_layernorm_bwd (saving only the
 # pre-activation).  GIGAPATH_TRAIN_FFN_FUSED=0 selects the plain torch composition for A/B runs.
 TRAIN_FFN_FUSED = os.environ.get("GIGAPATH_TRAIN_FFN_FUSED", "1") != "0"
@@ -684,11 +729,14 @@ def gelu_layernorm_torch(h: torch.Tensor, ln_weight: torch.Tensor, ln_bias: torc
                                           eps).to(h.dtype)
 
 
-def drop_path(x: torch.Tensor, drop_prob: float, training: bool) -> torch.Tensor:
+def drop_path(x: torch.Tensor, drop_prob: float, training: bool, slide_lens=None) -> torch.Tensor:
     """The reference's DropPath (timm's drop_path, torchscale/component/droppath.py): one Bernoulli(keep) draw per
-    batch element, the kept rows scaled by 1 / keep."""
+    batch element, the kept rows scaled by 1 / keep.  With slide_lens, x is a packed [1, T, E] stream and the draws
+    are one per slide (drop_path_scale)."""
     if drop_prob == 0.0 or not training:
         return x
+    if slide_lens is not None:
+        return x * drop_path_scale(1, drop_prob, training, x.device, slide_lens).view(1, -1, 1).to(x.dtype)
     keep = 1.0 - drop_prob
     mask = x.new_empty((x.shape[0],) + (1,) * (x.dim() - 1)).bernoulli_(keep)
     return x * (mask / keep)
@@ -707,10 +755,35 @@ def rows_fusable(E: int, p: float = 0.0) -> bool:
     return TRAIN_ROWS_FUSED and E in ROWS_TRAIN_COLS and 0.0 <= p < 1.0
 
 
-def drop_path_scale(B: int, drop_prob: float, training: bool, dev) -> Optional[torch.Tensor]:
-    """drop_path's per-batch-element factor mask / keep as a [B] fp32 vector (the same draw), or None for 1."""
+_SLIDE_LENS_DEV: "OrderedDict[tuple, torch.Tensor]" = OrderedDict()
+
+
+def _slide_lens_dev(slide_lens, dev) -> torch.Tensor:
+    """The slide lengths as an int64 device vector (a small cache: a step asks 2 * depth times for the same one)."""
+    key = (tuple(int(x) for x in slide_lens), str(dev))
+    t = _SLIDE_LENS_DEV.get(key)
+    if t is None:
+        while len(_SLIDE_LENS_DEV) >= 16:
+            _SLIDE_LENS_DEV.popitem(last=False)
+        t = _SLIDE_LENS_DEV[key] = torch.tensor(key[0], dtype=torch.int64, device=dev)
+    return t
+
+
+def drop_path_slide_factors(S: int, drop_prob: float, dev) -> torch.Tensor:
+    """One Bernoulli(keep) draw per slide, in slide order, scaled by 1 / keep: [S] fp32."""
+    keep = 1.0 - drop_prob
+    return torch.empty(S, dtype=torch.float32, device=dev).bernoulli_(keep) / keep
+
+
+def drop_path_scale(B: int, drop_prob: float, training: bool, dev, slide_lens=None) -> Optional[torch.Tensor]:
+    """drop_path's per-batch-element factor mask / keep as a [B] fp32 vector (the same draw), or None for 1.  With
+    slide_lens (a packed [1, T, E] stream) the draws are one per slide and the result is the per-row [T] vector: each
+    slide's factor repeated over its rows (rows_per_scale = 1 for the row kernels)."""
     if drop_prob == 0.0 or not training:
         return None
+    if slide_lens is not None:
+        f = drop_path_slide_factors(len(slide_lens), drop_prob, dev)
+        return torch.repeat_interleave(f, _slide_lens_dev(slide_lens, dev), output_size=int(sum(slide_lens)))
     keep = 1.0 - drop_prob
     return torch.empty(B, dtype=torch.float32, device=dev).bernoulli_(keep) / keep
 

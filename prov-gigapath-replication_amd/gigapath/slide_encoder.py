@@ -16,7 +16,8 @@ factor (see pos_embed.py); ``model.pos_embed`` is still available, built lazily 
 Training is opt-in: after ``model.enable_training()`` a forward under autograd (an input that requires grad, or
 ``.train()`` with a parameter that does) takes an eager differentiable path -- torch GEMMs and LayerNorms around the
 native attention backward (gp_dilated_attn_bwd) and the fused GELU + LayerNorm backward (gp_gelu_layernorm_bwd),
-with the reference's dropout and drop-path.  Without the opt-in, under ``torch.no_grad()`` or in ``.eval()`` without
+with the reference's dropout and drop-path.  ``forward_packed`` trains the same way on a mixed-length batch packed
+into one stream (one varlen attention backward per layer, gp_dilated_attn_bwd_varlen).  Without the opt-in, under ``torch.no_grad()`` or in ``.eval()`` without
 a grad-requiring input, every call is the inference path, bit for bit.
 """
 from __future__ import annotations
@@ -460,8 +461,14 @@ class LongNetViT(nn.Module):
         attention and branch merge run as one varlen launch each in which every slide keeps its
         own segment schedule (s = min(sl, L_i), no cross-slide attention).  Each slide's outputs
         are therefore those of its own B = 1 forward (up to the GEMMs' row-count-dependent
-        rounding).  Returns one output list per slide, as forward(x_i[None], c_i[None])."""
-        self.encoder.check_eval()
+        rounding).  Returns one output list per slide, as forward(x_i[None], c_i[None]).
+
+        Under autograd (enable_training(), runtime.takes_grad_path) the pack trains: the differentiable path of
+        forward() over the T packed rows, with one varlen attention backward per layer (_forward_packed_grad);
+        the outputs then carry grad_fn.  No HIP graph is captured on that path."""
+        grad_path = runtime.takes_grad_path(self, *[s[0] for s in slides])
+        if not grad_path:
+            self.encoder.check_eval()
         dev = self.cls_token.device
         xs, cs = [], []
         for x, c in slides:
@@ -475,6 +482,9 @@ class LongNetViT(nn.Module):
             cs.append(c if c.dtype in (torch.float32, torch.float64) else c.float())
         if not xs:
             return []
+        if grad_path and self._sp is not None and self._sp.world > 1:
+            raise RuntimeError("LongNetViT (MI355X path): training is single-device; call "
+                               "disable_sequence_parallel() first")
         if self._sp is not None and self._sp.world > 1:
             raise ValueError("forward_packed is single-device: disable sequence parallelism first")
         if self.encoder.layers[0].self_attn.head_dim != 48 or len({c.dtype for c in cs}) != 1 or \
@@ -486,6 +496,8 @@ class LongNetViT(nn.Module):
         c_cat = torch.cat(cs, 0)
         if self.validate_positions:
             self.check_positions([c_cat])
+        if grad_path:
+            return self._forward_packed_grad(x_cat, c_cat, Ns, all_layer_embed)
         if self.use_hip_graphs and not runtime.TIMER.enabled:
             self._packed_top(dev)
             self.encoder.engine.pack(self.encoder, dev)
@@ -509,6 +521,48 @@ class LongNetViT(nn.Module):
             res = self._forward_packed_device(x_cat, c_cat, Ns, all_layer_embed)
         out_dtype = self.norm.weight.dtype
         return [[res[k, i:i + 1].to(out_dtype) for k in range(res.shape[0])] for i in range(len(Ns))]
+
+    def _forward_packed_grad(self, x_cat, c_cat, Ns, all_layer_embed):
+        """The differentiable packed forward (eager): _forward_grad's chain over the T = sum(N_i + 1) packed rows --
+        patch F.linear over the concatenated tiles, the pos-embed rows (a constant), each slide's CLS row ahead of
+        its tiles, the layers on a [1, T, E] fp32 residual stream with the slide lengths (varlen attention core,
+        drop-path per slide) -- and the readouts per slide: the CLS rows at tok_off, or the mean over the slide's
+        tile rows with global_pool.  x_cat [sum N_i, C], c_cat [sum N_i, 2] -> one list per slide of [1, E]."""
+        dev = self.cls_token.device
+        E, S = self.embed_dim, len(Ns)
+        Ls = [n + 1 for n in Ns]
+        act = runtime.act_dtype()
+        proj = self.patch_embed.proj
+        xp = F.linear(x_cat.to(act), proj.weight.to(act), proj.bias.to(act))
+        with torch.no_grad():
+            pos = self.coords_to_pos(c_cat.detach(), self.tile_size)
+            rows = pos_rows(self._packed_top(dev)["tab"], pos, self.slide_ngrids)
+        tiles = xp.float() + rows
+        cls = self.cls_token.float().reshape(1, E)                # pos_embed row 0 is zero
+        parts, n0 = [], 0
+        for n in Ns:
+            parts += [cls, tiles[n0:n0 + n]]
+            n0 += n
+        h = torch.cat(parts, dim=0).unsqueeze(0)                  # [1, T, E]
+        states = [h]
+        h = run_layers_grad(self.encoder.layers, h, states.append, slide_lens=Ls)
+        if not all_layer_embed:
+            ln = self.encoder.layer_norm
+            states = [h if ln is None else F.layer_norm(h, (E,), ln.weight.float(), ln.bias.float(), ln.eps)]
+        out_dtype = self.norm.weight.dtype
+        nw, nb = self.norm.weight.float(), self.norm.bias.float()
+        tok_off = [0]
+        for L in Ls:
+            tok_off.append(tok_off[-1] + L)
+        cls_idx = torch.tensor(tok_off[:-1], dtype=torch.int64, device=dev)
+        outs = []
+        for s in states:
+            if self.global_pool:
+                pooled = torch.cat([s[:, tok_off[i] + 1:tok_off[i + 1], :].mean(dim=1) for i in range(S)], dim=0)
+            else:
+                pooled = s[0].index_select(0, cls_idx)
+            outs.append(F.layer_norm(pooled, (E,), nw, nb, self.norm.eps).to(out_dtype))
+        return [[o[i:i + 1] for o in outs] for i in range(S)]
 
     def _forward_packed_device(self, x_cat, c_cat, Ns, all_layer_embed):
         """Eager packed forward (captured as is by forward_packed): x_cat [sum N_i, C], c_cat

@@ -40,21 +40,25 @@ def _ln_grad(x32: torch.Tensor, ln: nn.LayerNorm) -> torch.Tensor:
     return F.layer_norm(x32, (x32.shape[-1],), ln.weight.float(), ln.bias.float(), ln.eps)
 
 
-def run_layers_grad(layers, x, on_state=None):
+def run_layers_grad(layers, x, on_state=None, slide_lens=None):
     """The chain of the layers' differentiable forwards on the fp32 residual stream x [B, L, E].  Each layer is
     handed the next layer's self_attn_layer_norm, so that layer i's last residual add and layer i + 1's first
     LayerNorm are one call (EncoderLayer._forward_grad); the per-layer states are the r outputs, the same bits as
-    calling the layers one by one."""
+    calling the layers one by one.  With slide_lens, x is [1, T, E]: the slides of those lengths packed token-major
+    (T = sum(slide_lens)); every row op runs over the T rows, the attention core is the varlen one and drop-path
+    draws once per slide."""
+    if slide_lens is not None and (x.dim() != 3 or x.shape[0] != 1 or x.shape[1] != sum(slide_lens)):
+        raise ValueError("run_layers_grad: a packed stream must be [1, sum(slide_lens), E], got %s" % (tuple(x.shape),))
     a = None
     n = len(layers)
     for i, layer in enumerate(layers):
         if not runtime.rows_fusable(layer.embed_dim, layer.dropout if layer.training else 0.0):
-            x, a = layer._forward_grad(x), None          # the torch composition, layer by layer
+            x, a = layer._forward_grad(x, slide_lens=slide_lens), None   # the torch composition, layer by layer
         elif i + 1 < n:
-            x, a = layer._forward_grad(x, a, layers[i + 1].self_attn_layer_norm)
+            x, a = layer._forward_grad(x, a, layers[i + 1].self_attn_layer_norm, slide_lens=slide_lens)
             a = a.reshape(-1, a.shape[-1])
         else:
-            x = layer._forward_grad(x, a)
+            x = layer._forward_grad(x, a, slide_lens=slide_lens)
         if on_state is not None:
             on_state(x)
     return x
@@ -83,7 +87,7 @@ class EncoderLayer(nn.Module):
         return DilatedAttention(args, embed_dim, args.encoder_attention_heads, dropout=args.attention_dropout,
                                 self_attention=True, subln=args.subln)
 
-    def _forward_grad(self, x, a_in=None, next_ln=None):
+    def _forward_grad(self, x, a_in=None, next_ln=None, slide_lens=None):
         """The differentiable path (reference encoder.py:116-162, pre-LN, alpha = 1) on an fp32 residual
         stream: LN -> self_attn -> dropout -> drop-path -> residual -> LN -> FFN -> drop-path -> residual.
 
@@ -92,34 +96,44 @@ class EncoderLayer(nn.Module):
         (runtime.resid_drop_ln_grad), FFN-output dropout + drop-path + residual (runtime.resid_drop_grad).
         A stack (run_layers_grad) hands over a_in, this layer's LN1 output computed by the previous layer's last
         call, and next_ln, the next layer's self_attn_layer_norm: the return value is then (r, next_ln(r) in the
-        16-bit format), the same bits as the two calls apart.  Both are ignored by the torch composition."""
+        16-bit format), the same bits as the two calls apart.  Both are ignored by the torch composition.
+
+        slide_lens: x is a packed [1, T, E] stream of slides of those lengths (run_layers_grad): the attention
+        core is the varlen one and drop-path draws one factor per slide, in slide order, for the slide's rows."""
         if self.training and self.self_attn.dropout > 0:
             raise RuntimeError("EncoderLayer (MI355X path): attention dropout is not implemented in training; "
                                "set attention_dropout=0")
         act = runtime.act_dtype()
         res = x.float()
         if runtime.rows_fusable(self.embed_dim, self.dropout if self.training else 0.0):
-            return self._forward_grad_fused(res, act, a_in, next_ln)
+            return self._forward_grad_fused(res, act, a_in, next_ln, slide_lens)
         a = _ln_grad(res, self.self_attn_layer_norm).to(act)
-        a, _ = self.self_attn(a, a, a)
+        a, _ = self._attn_grad(a, slide_lens)
         a = F.dropout(a.float(), self.dropout, self.training)
-        res = res + runtime.drop_path(a, self.drop_path_prob, self.training)
+        res = res + runtime.drop_path(a, self.drop_path_prob, self.training, slide_lens)
         f = self.ffn._forward_grad(_ln_grad(res, self.final_layer_norm).to(act))
-        return res + runtime.drop_path(f.float(), self.drop_path_prob, self.training)
+        return res + runtime.drop_path(f.float(), self.drop_path_prob, self.training, slide_lens)
 
-    def _forward_grad_fused(self, res, act, a_in, next_ln):
+    def _attn_grad(self, a, slide_lens):
+        """self_attn on the differentiable path: the module call, or for a packed stream its _forward_grad with the
+        slide lengths."""
+        if slide_lens is None:
+            return self.self_attn(a, a, a)
+        return self.self_attn._forward_grad(a, a, a, slide_lens=slide_lens)
+
+    def _forward_grad_fused(self, res, act, a_in, next_ln, slide_lens=None):
         B, L, E = res.shape
         M = B * L
         dev = res.device
         x2 = res.reshape(M, E)
         a = a_in if a_in is not None else runtime.layernorm_act_grad(x2, self.self_attn_layer_norm)
         a = a.view(B, L, E)
-        y, _ = self.self_attn(a, a, a)
-        s = runtime.drop_path_scale(B, self.drop_path_prob, self.training, dev)
+        y, _ = self._attn_grad(a, slide_lens)
+        s = runtime.drop_path_scale(B, self.drop_path_prob, self.training, dev, slide_lens)
         r, a2 = runtime.resid_drop_ln_grad(x2, y.reshape(M, E).to(act), self.final_layer_norm, self.dropout, s,
                                            self.training)
         f = self.ffn._forward_grad_core(a2)
-        s = runtime.drop_path_scale(B, self.drop_path_prob, self.training, dev)
+        s = runtime.drop_path_scale(B, self.drop_path_prob, self.training, dev, slide_lens)
         if next_ln is None:
             return runtime.resid_drop_grad(r, f, self.dropout, s, self.training).view(B, L, E)
         r2, a_next = runtime.resid_drop_ln_grad(r, f, next_ln, self.dropout, s, self.training)
@@ -127,11 +141,14 @@ class EncoderLayer(nn.Module):
 
     @runtime.compute_format
     def forward(self, x, encoder_padding_mask=None, attn_mask=None, rel_pos=None, multiway_split_position=None,
-                incremental_state=None):
+                incremental_state=None, slide_lens=None):
         if runtime.takes_grad_path(self, x):
             if x.device.type != "cuda":
                 raise RuntimeError("EncoderLayer (MI355X path) needs ROCm device tensors")
-            return self._forward_grad(x).to(x.dtype), None
+            return self._forward_grad(x, slide_lens=slide_lens).to(x.dtype), None
+        if slide_lens is not None:
+            raise RuntimeError("EncoderLayer (MI355X path): slide_lens is a training-path argument; inference packs "
+                               "slides through LongNetViT.forward_packed")
         if self.training and (self.dropout > 0 or self.drop_path_prob > 0):
             raise RuntimeError("EncoderLayer (MI355X path) is inference-only: call .eval()")
         B, L, E = x.shape

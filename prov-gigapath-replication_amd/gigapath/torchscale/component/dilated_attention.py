@@ -9,7 +9,8 @@ one fused QKV GEMM, ONE gp_dilated_attn_fwd launch for every (segment, dilation)
 Under autograd (an input that requires grad, or .train() with a parameter that does) the forward takes the
 differentiable path instead: the projections and inner_attn_ln in torch from the live parameters, and the
 attention core -- every branch and the merge -- through runtime.dilated_attention_grad, whose backward is one
-gp_dilated_attn_bwd call.  Dropout is not implemented; every other case is the inference path, unchanged.
+gp_dilated_attn_bwd call (for a packed stream of several slides, runtime.dilated_attention_grad_varlen and one
+gp_dilated_attn_bwd_varlen call).  Dropout is not implemented; every other case is the inference path, unchanged.
 """
 from __future__ import annotations
 
@@ -59,11 +60,16 @@ class DilatedAttention(nn.Module):
             return True
         return self.training and any(p.requires_grad for p in self.parameters())
 
-    def _forward_grad(self, query, key, value):
+    def _forward_grad(self, query, key, value, slide_lens=None):
         """The differentiable path: torch projections / LayerNorm around the native core.  The Q scale
-        D^-0.5 log2 e is folded into the Q weight and bias in fp32 before their cast, as PackedAttention does."""
+        D^-0.5 log2 e is folded into the Q weight and bias in fp32 before their cast, as PackedAttention does.
+        slide_lens: the input is [1, T, E], slides of those lengths packed token-major; the core is then
+        runtime.dilated_attention_grad_varlen (every slide its own segment schedule, D = 48)."""
         B, L, E = query.shape
         H, D = self.num_heads, self.head_dim
+        if slide_lens is not None and (B != 1 or L != sum(slide_lens)):
+            raise ValueError("DilatedAttention: a packed input must be [1, sum(slide_lens), E], got %s"
+                             % (tuple(query.shape),))
         act = runtime.act_dtype()
         prescaled = D in (48, 64)
         qs = (D ** -0.5) * runtime.LOG2E if prescaled else 1.0
@@ -79,8 +85,12 @@ class DilatedAttention(nn.Module):
         else:
             qkv = torch.cat([F.linear(t.reshape(M, E).to(act), w.to(act), b.to(act))
                              for t, w, b in ((query, wq, bq), (key, wk, bk), (value, wv, bv))], 1)
-        merged = runtime.dilated_attention_grad(qkv, B, L, H, D, self.args.segment_length, self.args.dilated_ratio,
-                                                prescaled)
+        if slide_lens is not None:
+            merged = runtime.dilated_attention_grad_varlen(qkv, slide_lens, H, D, self.args.segment_length,
+                                                           self.args.dilated_ratio)
+        else:
+            merged = runtime.dilated_attention_grad(qkv, B, L, H, D, self.args.segment_length,
+                                                    self.args.dilated_ratio, prescaled)
         ln = self.inner_attn_ln
         if runtime.rows_fusable(E):
             a = runtime.layernorm_act_grad(merged, ln)        # one kernel each way, merged the only tensor saved

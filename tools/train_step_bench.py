@@ -13,13 +13,21 @@ GIGAPATH_TRAIN_ROWS_FUSED=0, in one process:
             LN of the fp32 stream, LN of a 16-bit tensor; forward and backward; the add shapes at p = 0.1 and p = 0)
             with its achieved bytes/s over the algorithmic bytes against the 6.29 TB/s HBM rate
 
+  (d) packed  one training step (forward with all_layer_embed, a scalar loss, backward) of a mixed-length batch in
+            one process, two interleaved arms: LongNetViT.forward_packed (one varlen attention backward per layer),
+            and the same slides one per forward() call with gradients accumulated (the path without packing).  Two
+            batches: 16 slides of batch.mixed_batch_sizes(16, 500, 8000) (launch-bound) and 8 slides of
+            mixed_batch_sizes(8, 2000, 100000) (compute-bound); bf16 and fp16; ms (min - max), peak MiB, tiles/s
+
 The arms alternate round by round (HIP events on the launch stream, `warmup` untimed calls of each arm first,
 median over `rounds` x `iters`).  One JSON line per (part, format).
 
     python tools/train_step_bench.py [--parts op,step,rows] [--M 70001] [--F 3072] [--E 768] [--N 70000]
                                      [--rounds 7] [--iters 3] [--warmup 2] [--out profiles/train_step_bench.json]
+    python tools/train_step_bench.py --parts packed --out profiles/train_packed_bench.json
     python tools/train_step_bench.py --profile-steps 2          # fused steps only: the program of a
                                                                 # rocprofv3 --kernel-trace --stats run of its own
+    python tools/train_step_bench.py --profile-steps 2 --profile-packed   # the same for packed steps (small batch)
     python tools/train_step_bench.py --shares KERNEL_STATS.csv  # attention / GEMM / GELU+LN / rows / rest shares
 """
 import argparse
@@ -170,6 +178,70 @@ def bench_step(args, fmt):
     return rec
 
 
+PACKED_BATCHES = {"small": (16, 500, 8000), "large": (8, 2000, 100000)}
+
+
+def make_packed_steps(args, fmt, which):
+    """(packed step, sequential step, tiles) for one of PACKED_BATCHES on one model."""
+    import torch
+    import oracle as orc
+    from gigapath import batch, slide_encoder
+    dev = torch.device("cuda")
+    cfg = orc.arch_config("gigapath_slide_enc12l768d")
+    model = slide_encoder.create_model("", "gigapath_slide_enc12l768d", 1536, dropout=0.1, drop_path_rate=0.1)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in orc.make_weights(cfg, seed=0).items()}, strict=True)
+    model = model.to(dev).enable_training().train()
+    model.validate_positions = False                                       # no host sync inside the timed step
+    sizes = batch.mixed_batch_sizes(*PACKED_BATCHES[which])
+    slides = []
+    for i, n in enumerate(sizes):
+        x, c = orc.synthetic_slide(n, seed_x=100 + i, seed_c=200 + i)
+        slides.append((torch.from_numpy(x[0]).to(dev), torch.from_numpy(c[0]).to(dev)))
+
+    def loss_of(outs):
+        return sum(o.float().square().mean() for o in outs)
+
+    def packed():
+        for p in model.parameters():
+            p.grad = None
+        with torch.autocast("cuda", torch.float16, enabled=fmt == "fp16"):
+            outs = model.forward_packed(slides, all_layer_embed=True)
+        sum(loss_of(o) for o in outs).backward()
+
+    def sequential():
+        for p in model.parameters():
+            p.grad = None
+        for x, c in slides:
+            with torch.autocast("cuda", torch.float16, enabled=fmt == "fp16"):
+                outs = model(x[None], c[None], all_layer_embed=True)
+            loss_of(outs).backward()
+
+    return packed, sequential, sizes
+
+
+def bench_packed(args, fmt, which):
+    packed, sequential, sizes = make_packed_steps(args, fmt, which)
+    rec = {"tool": "train_step_bench", "part": "packed", "fmt": fmt, "batch": which, "slides": len(sizes),
+           "tiles": int(sum(sizes)), "sizes": sizes, "dropout": 0.1, "drop_path": 0.1}
+    for _ in range(args.warmup):
+        packed()
+        sequential()
+    times = {"packed": [], "sequential": []}
+    for _ in range(args.rounds):                                           # interleaved arms
+        times["packed"].append(timed(packed, args.iters))
+        times["sequential"].append(timed(sequential, args.iters))
+    for k, fn in (("packed", packed), ("sequential", sequential)):
+        med = statistics.median(times[k])
+        rec[k + "_ms"] = round(med, 3)
+        rec[k + "_ms_min_max"] = [round(min(times[k]), 3), round(max(times[k]), 3)]
+        rec[k + "_rounds_ms"] = [round(t, 3) for t in times[k]]
+        rec[k + "_peak_mib"] = round(peak_of(fn), 1)
+        rec[k + "_tiles_per_s"] = round(sum(sizes) / (med * 1e-3), 0)
+    rec["sequential_over_packed"] = round(rec["sequential_ms"] / rec["packed_ms"], 3)
+    rec["every_packed_round_below_every_sequential_round"] = max(times["packed"]) < min(times["sequential"])
+    return rec
+
+
 def bench_rows(args, dt, fmt):
     import torch
     from gigapath import _hip, runtime
@@ -261,6 +333,7 @@ def main():
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--profile-steps", type=int, default=0)
+    ap.add_argument("--profile-packed", action="store_true")
     ap.add_argument("--shares", default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -269,7 +342,7 @@ def main():
         lines.append(shares(args.shares))
     elif args.profile_steps:
         import torch
-        step = make_step(args, "bf16")
+        step = make_packed_steps(args, "bf16", "small")[0] if args.profile_packed else make_step(args, "bf16")
         for _ in range(args.profile_steps):
             step()
         torch.cuda.synchronize()
@@ -280,12 +353,17 @@ def main():
         _hip.load_library()
         for part in args.parts.split(","):
             for dt, fmt in ((torch.bfloat16, "bf16"), (torch.float16, "fp16")):
-                rec = {"op": bench_op, "rows": bench_rows}[part](args, dt, fmt) if part != "step" \
-                    else bench_step(args, fmt)
-                rec["rounds"], rec["iters"], rec["warmup"] = args.rounds, args.iters, args.warmup
-                rec["device"] = torch.cuda.get_device_name(0)
-                print(json.dumps(rec), flush=True)
-                lines.append(rec)
+                if part == "packed":
+                    recs = [bench_packed(args, fmt, which) for which in PACKED_BATCHES]
+                elif part == "step":
+                    recs = [bench_step(args, fmt)]
+                else:
+                    recs = [{"op": bench_op, "rows": bench_rows}[part](args, dt, fmt)]
+                for rec in recs:
+                    rec["rounds"], rec["iters"], rec["warmup"] = args.rounds, args.iters, args.warmup
+                    rec["device"] = torch.cuda.get_device_name(0)
+                    print(json.dumps(rec), flush=True)
+                    lines.append(rec)
                 torch.cuda.empty_cache()
     if args.shares:
         print(json.dumps(lines[0]), flush=True)
