@@ -619,6 +619,25 @@ int gp_ffn_fc2_ln_resid(const uint16_t* h, int64_t ldh, const uint16_t* W2g, int
                         float* s_out, int64_t M, int64_t N, int64_t F, void* ws, int64_t ws_bytes, int fmt,
                         void* stream);
 
+/* ---- Weight gradient of nn.Linear with the bias gradient fused (added under ABI 13; purely additive, the version
+ * stays 13): autograd's backward of the projections on the training path -- q/k/v/out_proj
+ * (multihead_attention.py:43-48), fc1 / fc2 (feedforward_network.py:131-142), the patch projection
+ * (slide_encoder.py:47-51) -- for the parameters:
+ *     dW[n, k] = sum_{m < M} dY[m, n] X[m, k]     fp32 [N, ldw]
+ *     db[n]    = sum_{m < M} dY[m, n]             fp32 [N], or NULL (no pass over dY of its own)
+ * dY [M, N] (row stride ldy) and X [M, K] (ldx) row-major in fmt (GP_FMT_BF16 or GP_FMT_F16; GP_FMT_F16_VBF16 is
+ * rejected); fp32 accumulation, dW / db written (not accumulated into) straight from the fp32 sums.  N and K
+ * multiples of 256; 1 <= M < 2^31; ldy, ldx multiples of 8, ldw of 4; operands 16-byte aligned.
+ * M is split into S chunks of whole 64-row steps, S a function of (M, N, K) alone (about 256 work items, no chunk
+ * under 256 rows): S == 1 writes dW / db directly; otherwise fp32 partials [S][N][K] + [S][N] go to the workspace
+ * (gp_linear_wgrad_workspace_bytes; 0 when S == 1 or the shape is unsupported; host only) and a second kernel adds
+ * them in chunk order.  No atomics and no dependence on the device: two calls, and two devices, give the same bits.
+ * A non-finite dY[m, n] makes row n of dW and db[n] non-finite and leaves every other row's bits (GradScaler relies
+ * on it).  Every argument error is rejected before any launch. */
+int64_t gp_linear_wgrad_workspace_bytes(int64_t M, int64_t N, int64_t K);
+int gp_linear_wgrad(const uint16_t* dY, int64_t ldy, const uint16_t* X, int64_t ldx, float* dW, int64_t ldw,
+                    float* db, int64_t M, int64_t N, int64_t K, void* ws, int64_t ws_bytes, int fmt, void* stream);
+
 /* Plain fp32 LayerNorm over rows with a row stride (readout: encoder.py:387-388,
  * slide_encoder.py:213-221).  out: [rows, cols] fp32 contiguous.  cols = 64 * {12, 16, 24}. */
 int gp_layernorm_f32(const float* x, int64_t row_stride, const float* ln_w, const float* ln_b,

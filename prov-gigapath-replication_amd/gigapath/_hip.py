@@ -110,8 +110,11 @@ SIGNATURES = {
                            c_i64, c_i64, c_i64, c_i32, c_vp],
     "gp_ffn_fc2_ln_resid": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64,
                             c_vp, c_f32, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i32, c_vp],
+    "gp_linear_wgrad_workspace_bytes": [c_i64, c_i64, c_i64],
+    "gp_linear_wgrad": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i32, c_vp],
 }
 _RESTYPES = {"gp_last_error_string": ctypes.c_char_p, "gp_varlen_plan_bytes": c_i64, "gp_gemm_workspace_bytes": c_i64,
+             "gp_linear_wgrad_workspace_bytes": c_i64,
              "gp_varlen_bwd_plan_bytes": c_i64,
              "gp_cls_attn_workspace_bytes": c_i64, "gp_attn_rows_plan_bytes": c_i64,
              "gp_seg_attn_bwd_workspace_bytes": ctypes.c_size_t,
@@ -563,6 +566,42 @@ def gelu_layernorm_bwd(h, dy, ln_w, eps, dh, dln_w=None, dln_b=None):
         nbytes = ws.numel()
     _check(lib.gp_gelu_layernorm_bwd(_ptr(h), _ptr(dy), _ptr(ln_w), eps, _ptr(dh), _ptr(dln_w), _ptr(dln_b),
                                      _ptr(ws), nbytes, rows, cols, fmt, _stream()), "gp_gelu_layernorm_bwd")
+
+
+WGRAD_TILE = 256
+
+
+def linear_wgrad_supported(M: int, N: int, K: int) -> bool:
+    """Whether gp_linear_wgrad covers dW [N, K] over M rows (N and K multiples of 256, 1 <= M < 2^31)."""
+    return 1 <= M < 2 ** 31 and N > 0 and K > 0 and N % WGRAD_TILE == 0 and K % WGRAD_TILE == 0
+
+
+def linear_wgrad(dy, x, dw, db=None, ws=None):
+    """dw[n, k] = sum_m dy[m, n] x[m, k] and (optionally) db[n] = sum_m dy[m, n] in fp32 (gp_linear_wgrad): dy
+    [M, N] and x [M, K] in one 16-bit format, unit column stride (row strides free, multiples of 8); dw [N, K] fp32
+    with unit column stride, db [N] fp32 contiguous or None.  ws: a uint8 device buffer of at least
+    gp_linear_wgrad_workspace_bytes(M, N, K) bytes; None takes the grow-only buffer of this device and stream."""
+    lib = load_library()
+    fmt = fmt_of(dy.dtype)
+    if dy.dim() != 2 or x.dim() != 2 or dw.dim() != 2 or x.shape[0] != dy.shape[0] or \
+            dw.shape != (dy.shape[1], x.shape[1]):
+        raise ValueError("linear_wgrad: dy [M, N], x [M, K], dw [N, K] expected, got %s %s %s"
+                         % (tuple(dy.shape), tuple(x.shape), tuple(dw.shape)))
+    for nm, t, dt in (("dy", dy, dy.dtype), ("x", x, dy.dtype), ("dw", dw, torch.float32)):
+        if not t.is_cuda or t.dtype != dt or t.stride(1) != 1:
+            raise ValueError("linear_wgrad: %s must be a %s device tensor with unit column stride" % (nm, dt))
+    if db is not None:
+        _dev(db, torch.float32, "db")
+        if db.numel() != dy.shape[1]:
+            raise ValueError("linear_wgrad: db has %d elements, N = %d" % (db.numel(), dy.shape[1]))
+    M, N = dy.shape
+    K = x.shape[1]
+    need = int(lib.gp_linear_wgrad_workspace_bytes(M, N, K))
+    if ws is None and need > 0:
+        ws = _bwd_workspace(dy.device, need)
+    nbytes = ws.numel() * ws.element_size() if ws is not None else 0
+    _check(lib.gp_linear_wgrad(_ptr(dy), dy.stride(0), _ptr(x), x.stride(0), _ptr(dw), dw.stride(0), _ptr(db), M, N, K,
+                               _ptr(ws), nbytes, fmt, _stream()), "gp_linear_wgrad")
 
 
 ROWS_TRAIN_COLS = (768, 1024, 1536)

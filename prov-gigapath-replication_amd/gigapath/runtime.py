@@ -729,6 +729,89 @@ def gelu_layernorm_torch(h: torch.Tensor, ln_weight: torch.Tensor, ln_bias: torc
                                           eps).to(h.dtype)
 
 
+# The projections' parameter gradients: dW = dY^T X and db = sum_rows dY as one gp_linear_wgrad call in fp32 (DESIGN
+# §3.13) instead of torch's 16-bit TN GEMM, its dY.sum(0) pass and the cat / cast backwards.  Opt-in:
+# GIGAPATH_TRAIN_WGRAD=1, or per model LongNetViT.enable_training(native_wgrad=True).
+TRAIN_WGRAD = os.environ.get("GIGAPATH_TRAIN_WGRAD", "0") == "1"
+
+
+def wgrad_enabled(module: torch.nn.Module) -> bool:
+    """The module's own switch (set by LongNetViT.enable_training(native_wgrad=...)), else the environment's."""
+    own = getattr(module, "native_wgrad", None)
+    return TRAIN_WGRAD if own is None else bool(own)
+
+
+def _linear_parts_act(parts, act):
+    """cat(w_i s_i).to(act), cat(b_i s_i).to(act): the operands of today's F.linear, bit for bit."""
+    ws = [w.float() * s if s != 1.0 else w.float() for w, _, s in parts]
+    bs = [b.float() * s if s != 1.0 else b.float() for _, b, s in parts]
+    if len(parts) == 1:
+        return ws[0].to(act), bs[0].to(act)
+    return torch.cat(ws, 0).to(act), torch.cat(bs, 0).to(act)
+
+
+def _wgrad_operand(t: torch.Tensor) -> torch.Tensor:
+    """t as gp_linear_wgrad reads it: unit column stride, a row stride that is a multiple of 8, 16-byte aligned."""
+    if t.stride(1) != 1 or t.stride(0) % 8 != 0 or t.stride(0) < t.shape[1] or t.data_ptr() % 16 != 0:
+        return t.contiguous()
+    return t
+
+
+class _LinearGrad(torch.autograd.Function):
+    """y = x . cat(w_i s_i)^T + cat(b_i s_i) in the activation format; backward: dX by torch's GEMM (the op autograd
+    runs for F.linear), dW / db of all parts by one gp_linear_wgrad call in fp32, sliced and scaled per part.  The
+    partials go to the grow-only backward workspace of this device and stream (_hip._bwd_workspace)."""
+
+    @staticmethod
+    def forward(ctx, x, scales, *wb):
+        parts = [(wb[2 * i], wb[2 * i + 1], scales[i]) for i in range(len(scales))]
+        w_act, b_act = _linear_parts_act(parts, x.dtype)
+        ctx.save_for_backward(x, w_act)
+        ctx.scales = scales
+        ctx.rows = [int(w.shape[0]) for w, _, _ in parts]
+        ctx.param_dtypes = [t.dtype for t in wb]
+        return torch.nn.functional.linear(x, w_act, b_act)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, w_act = ctx.saved_tensors
+        dy = dy.to(x.dtype)
+        dx = dy @ w_act if ctx.needs_input_grad[0] else None
+        need = ctx.needs_input_grad[2:]
+        grads = [None] * len(need)
+        if any(need):
+            N, K = w_act.shape
+            dw = torch.empty(N, K, dtype=torch.float32, device=x.device)
+            db = torch.empty(N, dtype=torch.float32, device=x.device) if any(need[1::2]) else None
+            _hip.linear_wgrad(_wgrad_operand(dy), _wgrad_operand(x), dw, db)
+            r0 = 0
+            for i, (n, s) in enumerate(zip(ctx.rows, ctx.scales)):
+                for j, full in ((2 * i, dw), (2 * i + 1, db)):
+                    if need[j]:
+                        gpart = full[r0:r0 + n]
+                        grads[j] = (gpart * s if s != 1.0 else gpart).to(ctx.param_dtypes[j])
+                r0 += n
+        return (dx, None) + tuple(grads)
+
+
+def linear_grad(x_act: torch.Tensor, parts) -> torch.Tensor:
+    """x_act [M, K] 16-bit, parts a list of (weight [N_i, K], bias [N_i], scale) -> x . cat(w_i s_i)^T + cat(b_i s_i)
+    [M, sum N_i] in x's format: the bits of F.linear(x, cat(w_i s_i).to(act), cat(b_i s_i).to(act)), with the
+    parameter gradients from gp_linear_wgrad (fp32, never rounded to 16 bits; three parts for a fused QKV, the Q
+    scale on the first).  Shapes the kernel does not cover (sum N_i or K no multiple of 256) take that F.linear
+    under autograd."""
+    parts = [(w, b, float(s)) for w, b, s in parts]
+    if x_act.dim() != 2 or x_act.dtype not in _hip.ACT_DTYPES:
+        raise ValueError("linear_grad: x must be [M, K] bf16 or fp16, got %s %s" % (tuple(x_act.shape), x_act.dtype))
+    M, K = x_act.shape
+    N = sum(int(w.shape[0]) for w, _, _ in parts)
+    if not x_act.is_cuda or not _hip.linear_wgrad_supported(M, N, K):
+        return torch.nn.functional.linear(x_act, *_linear_parts_act(parts, x_act.dtype))
+    flat = [t for w, b, _ in parts for t in (w, b)]
+    return _LinearGrad.apply(x_act, tuple(s for _, _, s in parts), *flat)
+
+
 def drop_path(x: torch.Tensor, drop_prob: float, training: bool, slide_lens=None) -> torch.Tensor:
     """The reference's DropPath (timm's drop_path, torchscale/component/droppath.py): one Bernoulli(keep) draw per
     batch element, the kept rows scaled by 1 / keep.  With slide_lens, x is a packed [1, T, E] stream and the draws

@@ -25,7 +25,7 @@ from __future__ import annotations
 import os
 from collections import OrderedDict
 from functools import partial
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -74,6 +74,7 @@ class LongNetViT(nn.Module):
     """LongNet slide encoder backbone (reference gigapath/slide_encoder.py:54-223)."""
 
     trainable = False       # opt-in to the differentiable path: enable_training()
+    native_wgrad = None     # projections' dW / db from gp_linear_wgrad: None = GIGAPATH_TRAIN_WGRAD (enable_training)
 
     def __init__(self, in_chans=1536, embed_dim=256, depth=12, slide_ngrids=1000, tile_size=256,
                  max_wsi_size=262144, norm_layer=nn.LayerNorm, global_pool=False, dropout=0.25,
@@ -129,13 +130,26 @@ class LongNetViT(nn.Module):
         return self
 
     # ---------------------------------------------------------------- training opt-in
-    def enable_training(self, flag: bool = True):
+    def enable_training(self, flag: bool = True, native_wgrad: Optional[bool] = None):
         """Opt this model, its encoder, every layer and every FFN in to (or out of) the differentiable path.
-        The path is taken only under autograd; inference calls are unchanged either way."""
+        The path is taken only under autograd; inference calls are unchanged either way.
+        native_wgrad: the projections' parameter gradients (patch projection, QKV, out-proj, fc1, fc2) from
+        gp_linear_wgrad in fp32 instead of torch's 16-bit GEMMs -- True / False sets the switch on this
+        model, its attentions and its FFNs; None leaves it as it is (never set: the environment's GIGAPATH_TRAIN_WGRAD,
+        default off)."""
         for m in self.modules():
             if hasattr(type(m), "trainable"):
                 m.trainable = bool(flag)
+            if native_wgrad is not None and hasattr(type(m), "native_wgrad"):
+                m.native_wgrad = bool(native_wgrad)
         return self
+
+    def _patch_proj_grad(self, x2d, act):
+        """The patch projection on the differentiable paths (x2d [rows, in_chans])."""
+        proj = self.patch_embed.proj
+        if runtime.wgrad_enabled(self):
+            return runtime.linear_grad(x2d.to(act), [(proj.weight, proj.bias, 1.0)])
+        return F.linear(x2d.to(act), proj.weight.to(act), proj.bias.to(act))
 
     # ---------------------------------------------------------------- init / helpers
     def initialize_vit_weights(self):
@@ -248,8 +262,7 @@ class LongNetViT(nn.Module):
         c = coords if coords.dtype in (torch.float32, torch.float64) else coords.float()
         if self.validate_positions:
             self.check_positions([c])
-        proj = self.patch_embed.proj
-        xp = F.linear(x.reshape(B * N, C).to(act), proj.weight.to(act), proj.bias.to(act)).view(B, N, E)
+        xp = self._patch_proj_grad(x.reshape(B * N, C), act).view(B, N, E)
         with torch.no_grad():
             pos = self.coords_to_pos(c.detach(), self.tile_size)
             rows = pos_rows(self._packed_top(dev)["tab"], pos, self.slide_ngrids)
@@ -532,8 +545,7 @@ class LongNetViT(nn.Module):
         E, S = self.embed_dim, len(Ns)
         Ls = [n + 1 for n in Ns]
         act = runtime.act_dtype()
-        proj = self.patch_embed.proj
-        xp = F.linear(x_cat.to(act), proj.weight.to(act), proj.bias.to(act))
+        xp = self._patch_proj_grad(x_cat, act)
         with torch.no_grad():
             pos = self.coords_to_pos(c_cat.detach(), self.tile_size)
             rows = pos_rows(self._packed_top(dev)["tab"], pos, self.slide_ngrids)

@@ -22,6 +22,8 @@ from ... import runtime
 
 
 class DilatedAttention(nn.Module):
+    native_wgrad = None     # projections' dW / db from gp_linear_wgrad: None = GIGAPATH_TRAIN_WGRAD (enable_training)
+
     def __init__(self, args, embed_dim, num_heads, dropout=0.0, self_attention=False,
                  encoder_decoder_attention=False, subln=False):
         super().__init__()
@@ -78,13 +80,20 @@ class DilatedAttention(nn.Module):
         def wb(lin, scale=1.0):
             return lin.weight.float() * scale, lin.bias.float() * scale
 
-        (wq, bq), (wk, bk), (wv, bv) = wb(self.q_proj, qs), wb(self.k_proj), wb(self.v_proj)
-        if key is query and value is query:
-            qkv = F.linear(query.reshape(M, E).to(act), torch.cat([wq, wk, wv], 0).to(act),
-                           torch.cat([bq, bk, bv], 0).to(act))
+        wgrad = runtime.wgrad_enabled(self)
+        fused = key is query and value is query
+        if fused and wgrad:
+            qkv = runtime.linear_grad(query.reshape(M, E).to(act), [(self.q_proj.weight, self.q_proj.bias, qs),
+                                                                    (self.k_proj.weight, self.k_proj.bias, 1.0),
+                                                                    (self.v_proj.weight, self.v_proj.bias, 1.0)])
         else:
-            qkv = torch.cat([F.linear(t.reshape(M, E).to(act), w.to(act), b.to(act))
-                             for t, w, b in ((query, wq, bq), (key, wk, bk), (value, wv, bv))], 1)
+            (wq, bq), (wk, bk), (wv, bv) = wb(self.q_proj, qs), wb(self.k_proj), wb(self.v_proj)
+            if fused:
+                qkv = F.linear(query.reshape(M, E).to(act), torch.cat([wq, wk, wv], 0).to(act),
+                               torch.cat([bq, bk, bv], 0).to(act))
+            else:
+                qkv = torch.cat([F.linear(t.reshape(M, E).to(act), w.to(act), b.to(act))
+                                 for t, w, b in ((query, wq, bq), (key, wk, bk), (value, wv, bv))], 1)
         if slide_lens is not None:
             merged = runtime.dilated_attention_grad_varlen(qkv, slide_lens, H, D, self.args.segment_length,
                                                            self.args.dilated_ratio)
@@ -96,7 +105,10 @@ class DilatedAttention(nn.Module):
             a = runtime.layernorm_act_grad(merged, ln)        # one kernel each way, merged the only tensor saved
         else:
             a = F.layer_norm(merged.float(), (E,), ln.weight.float(), ln.bias.float(), ln.eps).to(act)
-        out = F.linear(a, self.out_proj.weight.to(act), self.out_proj.bias.to(act))
+        if wgrad:
+            out = runtime.linear_grad(a, [(self.out_proj.weight, self.out_proj.bias, 1.0)])
+        else:
+            out = F.linear(a, self.out_proj.weight.to(act), self.out_proj.bias.to(act))
         return out.view(B, L, E).to(query.dtype), None
 
     @runtime.compute_format

@@ -20,6 +20,7 @@ from ... import _hip, runtime
 
 class FeedForwardNetwork(nn.Module):
     trainable = False       # opt-in to the differentiable path (LongNetViT.enable_training)
+    native_wgrad = None     # projections' dW / db from gp_linear_wgrad: None = GIGAPATH_TRAIN_WGRAD (enable_training)
 
     def __init__(self, embed_dim, ffn_dim, activation_fn="gelu", dropout=0.0, activation_dropout=0.0,
                  layernorm_eps=1e-5, subln=True):
@@ -41,12 +42,19 @@ class FeedForwardNetwork(nn.Module):
         shape = x.shape
         act = runtime.act_dtype()
         ln = self.ffn_layernorm
-        h = F.linear(x.reshape(-1, shape[-1]).to(act), self.fc1.weight.to(act), self.fc1.bias.to(act))
+        wgrad = runtime.wgrad_enabled(self)
+
+        def lin(t, fc):   # fc1 / fc2: F.linear, or the same bits with gp_linear_wgrad behind them
+            if wgrad:
+                return runtime.linear_grad(t, [(fc.weight, fc.bias, 1.0)])
+            return F.linear(t, fc.weight.to(act), fc.bias.to(act))
+
+        h = lin(x.reshape(-1, shape[-1]).to(act), self.fc1)
         if self.activation_dropout == 0 and runtime.TRAIN_FFN_FUSED and h.shape[1] in runtime.GELU_LN_COLS:
             y = runtime.gelu_layernorm_grad(h, ln.weight, ln.bias, ln.eps)
         else:
             y = runtime.gelu_layernorm_torch(h, ln.weight, ln.bias, ln.eps, self.activation_dropout, self.training)
-        return F.linear(y, self.fc2.weight.to(act), self.fc2.bias.to(act)).view(shape)
+        return lin(y, self.fc2).view(shape)
 
     def _forward_grad(self, x):
         """The differentiable path with the output dropout (standalone calls, and the layer's torch composition)."""

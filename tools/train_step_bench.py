@@ -19,12 +19,19 @@ GIGAPATH_TRAIN_ROWS_FUSED=0, in one process:
             batches: 16 slides of batch.mixed_batch_sizes(16, 500, 8000) (launch-bound) and 8 slides of
             mixed_batch_sizes(8, 2000, 100000) (compute-bound); bf16 and fp16; ms (min - max), peak MiB, tiles/s
 
+  (e) wgrad  gp_linear_wgrad (with its reduce launch) at M rows (default 70,001) for the five projections of the
+            768-wide arch -- QKV, out-proj, fc1, fc2, patch -- against what autograd runs for the same gradients:
+            dY.t() @ X in the 16-bit format, dY.sum(0), and the casts of both to fp32; ms and TF/s (2 M N K) per arm;
+            then the training step of (b) with GIGAPATH_TRAIN_WGRAD 0 against 1: ms and peak MiB
+
 The arms alternate round by round (HIP events on the launch stream, `warmup` untimed calls of each arm first,
 median over `rounds` x `iters`).  One JSON line per (part, format).
 
     python tools/train_step_bench.py [--parts op,step,rows] [--M 70001] [--F 3072] [--E 768] [--N 70000]
                                      [--rounds 7] [--iters 3] [--warmup 2] [--out profiles/train_step_bench.json]
     python tools/train_step_bench.py --parts packed --out profiles/train_packed_bench.json
+    python tools/train_step_bench.py --parts wgrad --out profiles/wgrad_bench.json
+    python tools/train_step_bench.py --profile-wgrad 3          # gp_linear_wgrad alone, for a rocprofv3 run of its own
     python tools/train_step_bench.py --profile-steps 2          # fused steps only: the program of a
                                                                 # rocprofv3 --kernel-trace --stats run of its own
     python tools/train_step_bench.py --profile-steps 2 --profile-packed   # the same for packed steps (small batch)
@@ -176,6 +183,56 @@ def bench_step(args, fmt):
     rec["rows_unfused_over_fused"] = round(rec["rows_unfused_ms"] / rec["fused_ms"], 3)
     rec["ffn_unfused_over_fused"] = round(rec["ffn_unfused_ms"] / rec["fused_ms"], 3)
     return rec
+
+
+# (N, K) of the 768-wide arch's projections: dW is [N, K]
+WGRAD_SHAPES = {"qkv": (2304, 768), "out_proj": (768, 768), "fc1": (3072, 768), "fc2": (768, 3072),
+                "patch": (768, 1536)}
+
+
+def wgrad_operands(M, N, K, dt):
+    import torch
+    dev = torch.device("cuda")
+    g = torch.Generator(device=dev).manual_seed(N + K)
+    return (torch.randn(M, N, device=dev, generator=g).to(dt), torch.randn(M, K, device=dev, generator=g).to(dt),
+            torch.empty(N, K, device=dev), torch.empty(N, device=dev))
+
+
+def bench_wgrad(args, dt, fmt):
+    from gigapath import _hip, runtime
+    recs = []
+    for name, (N, K) in WGRAD_SHAPES.items():
+        dy, x, dw, db = wgrad_operands(args.M, N, K, dt)
+
+        def native():
+            _hip.linear_wgrad(dy, x, dw, db)
+
+        def torch_arm():
+            return (dy.t() @ x).float(), dy.sum(0).float()
+
+        rec = {"tool": "train_step_bench", "part": "wgrad", "shape": name, "fmt": fmt, "M": args.M, "N": N, "K": K}
+        rec.update(abn({"native": native, "torch": torch_arm}, args))
+        for k in ("native", "torch"):
+            rec[k + "_tflops"] = round(2.0 * args.M * N * K / (rec[k + "_ms"] * 1e-3) / 1e12, 1)
+        rec["torch_over_native"] = round(rec["torch_ms"] / rec["native_ms"], 3)
+        recs.append(rec)
+        del dy, x, dw, db
+    step = make_step(args, fmt)
+
+    def arm(flag):
+        def go():
+            runtime.TRAIN_WGRAD = flag
+            step()
+        return go
+
+    rec = {"tool": "train_step_bench", "part": "wgrad_step", "fmt": fmt, "N": args.N, "dropout": 0.1, "drop_path": 0.1}
+    try:
+        rec.update(abn({"wgrad_off": arm(False), "wgrad_on": arm(True)}, args))
+    finally:
+        runtime.TRAIN_WGRAD = False
+    rec["off_over_on"] = round(rec["wgrad_off_ms"] / rec["wgrad_on_ms"], 3)
+    recs.append(rec)
+    return recs
 
 
 PACKED_BATCHES = {"small": (16, 500, 8000), "large": (8, 2000, 100000)}
@@ -334,12 +391,23 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--profile-steps", type=int, default=0)
     ap.add_argument("--profile-packed", action="store_true")
+    ap.add_argument("--profile-wgrad", type=int, default=0)
     ap.add_argument("--shares", default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     lines = []
     if args.shares:
         lines.append(shares(args.shares))
+    elif args.profile_wgrad:
+        import torch
+        from gigapath import _hip
+        for N, K in WGRAD_SHAPES.values():
+            dy, x, dw, db = wgrad_operands(args.M, N, K, torch.bfloat16)
+            for _ in range(args.profile_wgrad):
+                _hip.linear_wgrad(dy, x, dw, db)
+                (dy.t() @ x).float(), dy.sum(0).float()
+        torch.cuda.synchronize()
+        return
     elif args.profile_steps:
         import torch
         step = make_packed_steps(args, "bf16", "small")[0] if args.profile_packed else make_step(args, "bf16")
@@ -357,6 +425,8 @@ def main():
                     recs = [bench_packed(args, fmt, which) for which in PACKED_BATCHES]
                 elif part == "step":
                     recs = [bench_step(args, fmt)]
+                elif part == "wgrad":
+                    recs = bench_wgrad(args, dt, fmt)
                 else:
                     recs = [{"op": bench_op, "rows": bench_rows}[part](args, dt, fmt)]
                 for rec in recs:
