@@ -638,6 +638,19 @@ int64_t gp_linear_wgrad_workspace_bytes(int64_t M, int64_t N, int64_t K);
 int gp_linear_wgrad(const uint16_t* dY, int64_t ldy, const uint16_t* X, int64_t ldx, float* dW, int64_t ldw,
                     float* db, int64_t M, int64_t N, int64_t K, void* ws, int64_t ws_bytes, int fmt, void* stream);
 
+/* ---- Data gradient of nn.Linear (added under ABI 13; purely additive, the version stays 13): autograd's backward
+ * of the q/k/v/out_proj, fc1 and fc2 projections of the training path for their input:
+ *     dX[m, k] = sum_{n < N} dY[m, n] W[n, k]     [M, ldx] in fmt
+ * dY [M, N] (row stride ldy) and W [N, K] (ldw) row-major in fmt (GP_FMT_BF16 or GP_FMT_F16; GP_FMT_F16_VBF16 is
+ * rejected); W is contracted over its rows as stored (no transposed copy).  fp32 accumulation, dX rounded once to
+ * fmt and written (not accumulated into).  N and K multiples of 256; 1 <= M < 2^31; ldy, ldw, ldx multiples of 8;
+ * operands 16-byte aligned.  One 256 x 256 output tile per workgroup over the whole reduction: no workspace, no
+ * split over N, no atomics -- the bits are a function of the operands alone.  A non-finite dY[m, n] makes row m of
+ * dX non-finite and leaves every other row's bits.  Nothing past row M of dX or past column K of a wider dX row is
+ * written; rows of dY past M are not read.  Every argument error is rejected before any launch. */
+int gp_linear_dgrad(const uint16_t* dY, int64_t ldy, const uint16_t* W, int64_t ldw, uint16_t* dX, int64_t ldx,
+                    int64_t M, int64_t N, int64_t K, int fmt, void* stream);
+
 /* Plain fp32 LayerNorm over rows with a row stride (readout: encoder.py:387-388,
  * slide_encoder.py:213-221).  out: [rows, cols] fp32 contiguous.  cols = 64 * {12, 16, 24}. */
 int gp_layernorm_f32(const float* x, int64_t row_stride, const float* ln_w, const float* ln_b,

@@ -112,6 +112,7 @@ SIGNATURES = {
                             c_vp, c_f32, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i32, c_vp],
     "gp_linear_wgrad_workspace_bytes": [c_i64, c_i64, c_i64],
     "gp_linear_wgrad": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i32, c_vp],
+    "gp_linear_dgrad": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_i32, c_vp],
 }
 _RESTYPES = {"gp_last_error_string": ctypes.c_char_p, "gp_varlen_plan_bytes": c_i64, "gp_gemm_workspace_bytes": c_i64,
              "gp_linear_wgrad_workspace_bytes": c_i64,
@@ -602,6 +603,43 @@ def linear_wgrad(dy, x, dw, db=None, ws=None):
     nbytes = ws.numel() * ws.element_size() if ws is not None else 0
     _check(lib.gp_linear_wgrad(_ptr(dy), dy.stride(0), _ptr(x), x.stride(0), _ptr(dw), dw.stride(0), _ptr(db), M, N, K,
                                _ptr(ws), nbytes, fmt, _stream()), "gp_linear_wgrad")
+
+
+# (N, K) at which torch's NN GEMM measured faster than gp_linear_dgrad on the MI355X at M = 70,001 (DESIGN §3.14:
+# by 1 - 8 %, bf16 and fp16): the 768-wide arch's QKV, out-proj, fc1 and fc2.  The training path leaves them to torch;
+# linear_dgrad itself runs them.  The list is keyed on (N, K) alone and holds at every M, though M = 70,001 is the only
+# row count measured.  The other archs' shapes are not measured either: with the switch on they go to the kernel.
+DGRAD_TORCH_FASTER = frozenset({(2304, 768), (768, 768), (3072, 768), (768, 3072)})
+
+
+def linear_dgrad_supported(M: int, N: int, K: int) -> bool:
+    """Whether the training path takes dX [M, K] over a reduction of N from gp_linear_dgrad: a shape the kernel
+    covers (N and K multiples of 256, 1 <= M < 2^31) at which torch's GEMM did not measure faster."""
+    return 1 <= M < 2 ** 31 and N > 0 and K > 0 and N % WGRAD_TILE == 0 and K % WGRAD_TILE == 0 and \
+        (N, K) not in DGRAD_TORCH_FASTER
+
+
+def linear_dgrad(dy, w, dx=None):
+    """dx[m, k] = sum_n dy[m, n] w[n, k] (gp_linear_dgrad): dy [M, N], w [N, K] and dx [M, K] in one 16-bit format,
+    unit column stride (row strides free, multiples of 8); fp32 accumulation, dx rounded once.  dx None: a new
+    contiguous tensor.  Returns dx."""
+    lib = load_library()
+    fmt = fmt_of(dy.dtype)
+    if dy.dim() != 2 or w.dim() != 2 or w.shape[0] != dy.shape[1]:
+        raise ValueError("linear_dgrad: dy [M, N], w [N, K] expected, got %s %s" % (tuple(dy.shape), tuple(w.shape)))
+    if dx is None:
+        dx = torch.empty(dy.shape[0], w.shape[1], dtype=dy.dtype, device=dy.device)
+    if dx.dim() != 2 or dx.shape != (dy.shape[0], w.shape[1]):
+        raise ValueError("linear_dgrad: dx [M, K] = %s expected, got %s"
+                         % ((dy.shape[0], w.shape[1]), tuple(dx.shape)))
+    for nm, t in (("dy", dy), ("w", w), ("dx", dx)):
+        if not t.is_cuda or t.dtype != dy.dtype or t.stride(1) != 1:
+            raise ValueError("linear_dgrad: %s must be a %s device tensor with unit column stride" % (nm, dy.dtype))
+    M, N = dy.shape
+    K = w.shape[1]
+    _check(lib.gp_linear_dgrad(_ptr(dy), dy.stride(0), _ptr(w), w.stride(0), _ptr(dx), dx.stride(0), M, N, K, fmt,
+                               _stream()), "gp_linear_dgrad")
+    return dx
 
 
 ROWS_TRAIN_COLS = (768, 1024, 1536)

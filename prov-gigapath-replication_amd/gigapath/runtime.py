@@ -741,6 +741,17 @@ def wgrad_enabled(module: torch.nn.Module) -> bool:
     return TRAIN_WGRAD if own is None else bool(own)
 
 
+# The projections' data gradient dX = dY W as gp_linear_dgrad instead of torch's NN GEMM.  Opt-in:
+# GIGAPATH_TRAIN_DGRAD=1, or per model LongNetViT.enable_training(native_dgrad=True).  Independent of TRAIN_WGRAD.
+TRAIN_DGRAD = os.environ.get("GIGAPATH_TRAIN_DGRAD", "0") == "1"
+
+
+def dgrad_enabled(module: torch.nn.Module) -> bool:
+    """The module's own switch (set by LongNetViT.enable_training(native_dgrad=...)), else the environment's."""
+    own = getattr(module, "native_dgrad", None)
+    return TRAIN_DGRAD if own is None else bool(own)
+
+
 def _linear_parts_act(parts, act):
     """cat(w_i s_i).to(act), cat(b_i s_i).to(act): the operands of today's F.linear, bit for bit."""
     ws = [w.float() * s if s != 1.0 else w.float() for w, _, s in parts]
@@ -758,16 +769,19 @@ def _wgrad_operand(t: torch.Tensor) -> torch.Tensor:
 
 
 class _LinearGrad(torch.autograd.Function):
-    """y = x . cat(w_i s_i)^T + cat(b_i s_i) in the activation format; backward: dX by torch's GEMM (the op autograd
-    runs for F.linear), dW / db of all parts by one gp_linear_wgrad call in fp32, sliced and scaled per part.  The
-    partials go to the grow-only backward workspace of this device and stream (_hip._bwd_workspace)."""
+    """y = x . cat(w_i s_i)^T + cat(b_i s_i) in the activation format.  Backward, by the two switches: dX from
+    gp_linear_dgrad (dgrad) or torch's GEMM (the op autograd runs for F.linear); dW / db of all parts by one
+    gp_linear_wgrad call in fp32 (wgrad; the partials go to the grow-only backward workspace of this device and
+    stream, _hip._bwd_workspace) or by the expressions autograd evaluates, dy^T x and dy.sum(0) in the format --
+    either way sliced and scaled per part."""
 
     @staticmethod
-    def forward(ctx, x, scales, *wb):
+    def forward(ctx, x, scales, wgrad, dgrad, *wb):
         parts = [(wb[2 * i], wb[2 * i + 1], scales[i]) for i in range(len(scales))]
         w_act, b_act = _linear_parts_act(parts, x.dtype)
         ctx.save_for_backward(x, w_act)
         ctx.scales = scales
+        ctx.wgrad, ctx.dgrad = wgrad, dgrad
         ctx.rows = [int(w.shape[0]) for w, _, _ in parts]
         ctx.param_dtypes = [t.dtype for t in wb]
         return torch.nn.functional.linear(x, w_act, b_act)
@@ -777,14 +791,20 @@ class _LinearGrad(torch.autograd.Function):
     def backward(ctx, dy):
         x, w_act = ctx.saved_tensors
         dy = dy.to(x.dtype)
-        dx = dy @ w_act if ctx.needs_input_grad[0] else None
-        need = ctx.needs_input_grad[2:]
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = _hip.linear_dgrad(_wgrad_operand(dy), _wgrad_operand(w_act)) if ctx.dgrad else dy @ w_act
+        need = ctx.needs_input_grad[4:]
         grads = [None] * len(need)
         if any(need):
             N, K = w_act.shape
-            dw = torch.empty(N, K, dtype=torch.float32, device=x.device)
-            db = torch.empty(N, dtype=torch.float32, device=x.device) if any(need[1::2]) else None
-            _hip.linear_wgrad(_wgrad_operand(dy), _wgrad_operand(x), dw, db)
+            if ctx.wgrad:
+                dw = torch.empty(N, K, dtype=torch.float32, device=x.device)
+                db = torch.empty(N, dtype=torch.float32, device=x.device) if any(need[1::2]) else None
+                _hip.linear_wgrad(_wgrad_operand(dy), _wgrad_operand(x), dw, db)
+            else:
+                dw = (dy.t() @ x).float() if any(need[0::2]) else None
+                db = dy.sum(0).float() if any(need[1::2]) else None
             r0 = 0
             for i, (n, s) in enumerate(zip(ctx.rows, ctx.scales)):
                 for j, full in ((2 * i, dw), (2 * i + 1, db)):
@@ -792,24 +812,27 @@ class _LinearGrad(torch.autograd.Function):
                         gpart = full[r0:r0 + n]
                         grads[j] = (gpart * s if s != 1.0 else gpart).to(ctx.param_dtypes[j])
                 r0 += n
-        return (dx, None) + tuple(grads)
+        return (dx, None, None, None) + tuple(grads)
 
 
-def linear_grad(x_act: torch.Tensor, parts) -> torch.Tensor:
+def linear_grad(x_act: torch.Tensor, parts, wgrad: bool = True, dgrad: bool = False) -> torch.Tensor:
     """x_act [M, K] 16-bit, parts a list of (weight [N_i, K], bias [N_i], scale) -> x . cat(w_i s_i)^T + cat(b_i s_i)
-    [M, sum N_i] in x's format: the bits of F.linear(x, cat(w_i s_i).to(act), cat(b_i s_i).to(act)), with the
+    [M, sum N_i] in x's format: the bits of F.linear(x, cat(w_i s_i).to(act), cat(b_i s_i).to(act)).  wgrad: the
     parameter gradients from gp_linear_wgrad (fp32, never rounded to 16 bits; three parts for a fused QKV, the Q
-    scale on the first).  Shapes the kernel does not cover (sum N_i or K no multiple of 256) take that F.linear
-    under autograd."""
+    scale on the first).  dgrad: the input gradient from gp_linear_dgrad.  Each switch holds on its own; with both
+    off, on CPU tensors and for shapes neither kernel covers (sum N_i or K no multiple of 256) the call is that
+    F.linear under autograd; a shape only the data-gradient kernel leaves out takes torch's dy @ w."""
     parts = [(w, b, float(s)) for w, b, s in parts]
     if x_act.dim() != 2 or x_act.dtype not in _hip.ACT_DTYPES:
         raise ValueError("linear_grad: x must be [M, K] bf16 or fp16, got %s %s" % (tuple(x_act.shape), x_act.dtype))
     M, K = x_act.shape
     N = sum(int(w.shape[0]) for w, _, _ in parts)
-    if not x_act.is_cuda or not _hip.linear_wgrad_supported(M, N, K):
+    wgrad = bool(wgrad) and x_act.is_cuda and _hip.linear_wgrad_supported(M, N, K)
+    dgrad = bool(dgrad) and x_act.is_cuda and _hip.linear_dgrad_supported(M, N, K)
+    if not (wgrad or dgrad):
         return torch.nn.functional.linear(x_act, *_linear_parts_act(parts, x_act.dtype))
     flat = [t for w, b, _ in parts for t in (w, b)]
-    return _LinearGrad.apply(x_act, tuple(s for _, _, s in parts), *flat)
+    return _LinearGrad.apply(x_act, tuple(s for _, _, s in parts), wgrad, dgrad, *flat)
 
 
 def drop_path(x: torch.Tensor, drop_prob: float, training: bool, slide_lens=None) -> torch.Tensor:

@@ -75,6 +75,7 @@ class LongNetViT(nn.Module):
 
     trainable = False       # opt-in to the differentiable path: enable_training()
     native_wgrad = None     # projections' dW / db from gp_linear_wgrad: None = GIGAPATH_TRAIN_WGRAD (enable_training)
+    native_dgrad = None     # projections' dX from gp_linear_dgrad: None = GIGAPATH_TRAIN_DGRAD (enable_training)
 
     def __init__(self, in_chans=1536, embed_dim=256, depth=12, slide_ngrids=1000, tile_size=256,
                  max_wsi_size=262144, norm_layer=nn.LayerNorm, global_pool=False, dropout=0.25,
@@ -130,25 +131,31 @@ class LongNetViT(nn.Module):
         return self
 
     # ---------------------------------------------------------------- training opt-in
-    def enable_training(self, flag: bool = True, native_wgrad: Optional[bool] = None):
+    def enable_training(self, flag: bool = True, native_wgrad: Optional[bool] = None,
+                        native_dgrad: Optional[bool] = None):
         """Opt this model, its encoder, every layer and every FFN in to (or out of) the differentiable path.
         The path is taken only under autograd; inference calls are unchanged either way.
         native_wgrad: the projections' parameter gradients (patch projection, QKV, out-proj, fc1, fc2) from
         gp_linear_wgrad in fp32 instead of torch's 16-bit GEMMs -- True / False sets the switch on this
         model, its attentions and its FFNs; None leaves it as it is (never set: the environment's GIGAPATH_TRAIN_WGRAD,
-        default off)."""
+        default off).
+        native_dgrad: the same switch for the projections' input gradients (QKV, out-proj, fc1, fc2) from
+        gp_linear_dgrad instead of torch's GEMM (the environment's GIGAPATH_TRAIN_DGRAD, default off)."""
         for m in self.modules():
             if hasattr(type(m), "trainable"):
                 m.trainable = bool(flag)
             if native_wgrad is not None and hasattr(type(m), "native_wgrad"):
                 m.native_wgrad = bool(native_wgrad)
+            if native_dgrad is not None and hasattr(type(m), "native_dgrad"):
+                m.native_dgrad = bool(native_dgrad)
         return self
 
     def _patch_proj_grad(self, x2d, act):
         """The patch projection on the differentiable paths (x2d [rows, in_chans])."""
         proj = self.patch_embed.proj
-        if runtime.wgrad_enabled(self):
-            return runtime.linear_grad(x2d.to(act), [(proj.weight, proj.bias, 1.0)])
+        wgrad, dgrad = runtime.wgrad_enabled(self), runtime.dgrad_enabled(self)
+        if wgrad or dgrad:   # (the tile features need no gradient: gp_linear_dgrad never runs here)
+            return runtime.linear_grad(x2d.to(act), [(proj.weight, proj.bias, 1.0)], wgrad, dgrad)
         return F.linear(x2d.to(act), proj.weight.to(act), proj.bias.to(act))
 
     # ---------------------------------------------------------------- init / helpers

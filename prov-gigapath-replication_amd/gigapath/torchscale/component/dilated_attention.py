@@ -23,6 +23,7 @@ from ... import runtime
 
 class DilatedAttention(nn.Module):
     native_wgrad = None     # projections' dW / db from gp_linear_wgrad: None = GIGAPATH_TRAIN_WGRAD (enable_training)
+    native_dgrad = None     # projections' dX from gp_linear_dgrad: None = GIGAPATH_TRAIN_DGRAD (enable_training)
 
     def __init__(self, args, embed_dim, num_heads, dropout=0.0, self_attention=False,
                  encoder_decoder_attention=False, subln=False):
@@ -80,12 +81,13 @@ class DilatedAttention(nn.Module):
         def wb(lin, scale=1.0):
             return lin.weight.float() * scale, lin.bias.float() * scale
 
-        wgrad = runtime.wgrad_enabled(self)
+        wgrad, dgrad = runtime.wgrad_enabled(self), runtime.dgrad_enabled(self)
         fused = key is query and value is query
-        if fused and wgrad:
+        if fused and (wgrad or dgrad):
             qkv = runtime.linear_grad(query.reshape(M, E).to(act), [(self.q_proj.weight, self.q_proj.bias, qs),
                                                                     (self.k_proj.weight, self.k_proj.bias, 1.0),
-                                                                    (self.v_proj.weight, self.v_proj.bias, 1.0)])
+                                                                    (self.v_proj.weight, self.v_proj.bias, 1.0)],
+                                     wgrad, dgrad)
         else:
             (wq, bq), (wk, bk), (wv, bv) = wb(self.q_proj, qs), wb(self.k_proj), wb(self.v_proj)
             if fused:
@@ -105,8 +107,8 @@ class DilatedAttention(nn.Module):
             a = runtime.layernorm_act_grad(merged, ln)        # one kernel each way, merged the only tensor saved
         else:
             a = F.layer_norm(merged.float(), (E,), ln.weight.float(), ln.bias.float(), ln.eps).to(act)
-        if wgrad:
-            out = runtime.linear_grad(a, [(self.out_proj.weight, self.out_proj.bias, 1.0)])
+        if wgrad or dgrad:
+            out = runtime.linear_grad(a, [(self.out_proj.weight, self.out_proj.bias, 1.0)], wgrad, dgrad)
         else:
             out = F.linear(a, self.out_proj.weight.to(act), self.out_proj.bias.to(act))
         return out.view(B, L, E).to(query.dtype), None

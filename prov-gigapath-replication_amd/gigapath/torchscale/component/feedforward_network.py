@@ -21,6 +21,7 @@ from ... import _hip, runtime
 class FeedForwardNetwork(nn.Module):
     trainable = False       # opt-in to the differentiable path (LongNetViT.enable_training)
     native_wgrad = None     # projections' dW / db from gp_linear_wgrad: None = GIGAPATH_TRAIN_WGRAD (enable_training)
+    native_dgrad = None     # projections' dX from gp_linear_dgrad: None = GIGAPATH_TRAIN_DGRAD (enable_training)
 
     def __init__(self, embed_dim, ffn_dim, activation_fn="gelu", dropout=0.0, activation_dropout=0.0,
                  layernorm_eps=1e-5, subln=True):
@@ -42,11 +43,11 @@ class FeedForwardNetwork(nn.Module):
         shape = x.shape
         act = runtime.act_dtype()
         ln = self.ffn_layernorm
-        wgrad = runtime.wgrad_enabled(self)
+        wgrad, dgrad = runtime.wgrad_enabled(self), runtime.dgrad_enabled(self)
 
-        def lin(t, fc):   # fc1 / fc2: F.linear, or the same bits with gp_linear_wgrad behind them
-            if wgrad:
-                return runtime.linear_grad(t, [(fc.weight, fc.bias, 1.0)])
+        def lin(t, fc):   # fc1 / fc2: F.linear, or the same bits with gp_linear_wgrad / gp_linear_dgrad behind them
+            if wgrad or dgrad:
+                return runtime.linear_grad(t, [(fc.weight, fc.bias, 1.0)], wgrad, dgrad)
             return F.linear(t, fc.weight.to(act), fc.bias.to(act))
 
         h = lin(x.reshape(-1, shape[-1]).to(act), self.fc1)

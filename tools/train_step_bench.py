@@ -24,6 +24,11 @@ GIGAPATH_TRAIN_ROWS_FUSED=0, in one process:
             dY.t() @ X in the 16-bit format, dY.sum(0), and the casts of both to fp32; ms and TF/s (2 M N K) per arm;
             then the training step of (b) with GIGAPATH_TRAIN_WGRAD 0 against 1: ms and peak MiB
 
+  (f) dgrad  gp_linear_dgrad at M rows (default 70,001) for the four projections of the 768-wide arch whose input
+            needs a gradient -- QKV, out-proj, fc1, fc2 -- against torch's dY @ W in the 16-bit format: ms and TF/s
+            (2 M N K) per arm; then the training step of (b) with GIGAPATH_TRAIN_WGRAD 1 and GIGAPATH_TRAIN_DGRAD 0
+            against 1: ms and peak MiB
+
 The arms alternate round by round (HIP events on the launch stream, `warmup` untimed calls of each arm first,
 median over `rounds` x `iters`).  One JSON line per (part, format).
 
@@ -31,6 +36,7 @@ median over `rounds` x `iters`).  One JSON line per (part, format).
                                      [--rounds 7] [--iters 3] [--warmup 2] [--out profiles/train_step_bench.json]
     python tools/train_step_bench.py --parts packed --out profiles/train_packed_bench.json
     python tools/train_step_bench.py --parts wgrad --out profiles/wgrad_bench.json
+    python tools/train_step_bench.py --parts dgrad --out profiles/dgrad_bench.json
     python tools/train_step_bench.py --profile-wgrad 3          # gp_linear_wgrad alone, for a rocprofv3 run of its own
     python tools/train_step_bench.py --profile-steps 2          # fused steps only: the program of a
                                                                 # rocprofv3 --kernel-trace --stats run of its own
@@ -235,6 +241,56 @@ def bench_wgrad(args, dt, fmt):
     return recs
 
 
+# (N, K) of the 768-wide arch's projections whose input needs a gradient: dX [M, K] over a reduction of N
+DGRAD_SHAPES = {"qkv": (2304, 768), "out_proj": (768, 768), "fc1": (3072, 768), "fc2": (768, 3072)}
+
+
+def bench_dgrad(args, dt, fmt):
+    import torch
+    from gigapath import _hip, runtime
+    dev = torch.device("cuda")
+    recs = []
+    for name, (N, K) in DGRAD_SHAPES.items():
+        g = torch.Generator(device=dev).manual_seed(N + K)
+        dy = torch.randn(args.M, N, device=dev, generator=g).to(dt)
+        w = (0.03 * torch.randn(N, K, device=dev, generator=g)).to(dt)
+        dx = torch.empty(args.M, K, device=dev, dtype=dt)
+
+        def native():
+            _hip.linear_dgrad(dy, w, dx)
+
+        def torch_arm():
+            return dy @ w
+
+        rec = {"tool": "train_step_bench", "part": "dgrad", "shape": name, "fmt": fmt, "M": args.M, "N": N, "K": K}
+        rec.update(abn({"native": native, "torch": torch_arm}, args))
+        for k in ("native", "torch"):
+            rec[k + "_tflops"] = round(2.0 * args.M * N * K / (rec[k + "_ms"] * 1e-3) / 1e12, 1)
+        rec["torch_over_native"] = round(rec["torch_ms"] / rec["native_ms"], 3)
+        recs.append(rec)
+        del dy, w, dx
+    step = make_step(args, fmt)
+
+    def arm(flag):
+        def go():
+            runtime.TRAIN_WGRAD, runtime.TRAIN_DGRAD = True, flag
+            step()
+        return go
+
+    rec = {"tool": "train_step_bench", "part": "dgrad_step", "fmt": fmt, "N": args.N, "dropout": 0.1, "drop_path": 0.1,
+           "wgrad": True}
+    left_to_torch = _hip.DGRAD_TORCH_FASTER
+    try:
+        _hip.DGRAD_TORCH_FASTER = frozenset()        # the on arm runs the kernel at every shape it covers
+        rec.update(abn({"dgrad_off": arm(False), "dgrad_on": arm(True)}, args))
+    finally:
+        _hip.DGRAD_TORCH_FASTER = left_to_torch
+        runtime.TRAIN_WGRAD = runtime.TRAIN_DGRAD = False
+    rec["off_over_on"] = round(rec["dgrad_off_ms"] / rec["dgrad_on_ms"], 3)
+    recs.append(rec)
+    return recs
+
+
 PACKED_BATCHES = {"small": (16, 500, 8000), "large": (8, 2000, 100000)}
 
 
@@ -427,6 +483,8 @@ def main():
                     recs = [bench_step(args, fmt)]
                 elif part == "wgrad":
                     recs = bench_wgrad(args, dt, fmt)
+                elif part == "dgrad":
+                    recs = bench_dgrad(args, dt, fmt)
                 else:
                     recs = [{"op": bench_op, "rows": bench_rows}[part](args, dt, fmt)]
                 for rec in recs:
