@@ -323,9 +323,11 @@ int gp_branch_merge_ln_rows(const uint16_t* const* o_in, const float* const* lse
  *   [nseg_ib, H, m_ib] regions).  Otherwise also fills plan_host with the work table (device
  *   pointers into qkv / o / lse, not dereferenced here); the caller copies the plan_bytes to a
  *   16-byte aligned device buffer (plan_dev) that stays alive while launches use it.
- * gp_dilated_attn_fwd_varlen: every slide's five-branch attention in one launch (D = 48,
- *   q pre-scaled by D^-1/2 * log2 e).
- * gp_branch_merge_ln_varlen: every packed token's LSE merge + inner LN (E = 768, D = 48);
+ * gp_dilated_attn_fwd_varlen: every slide's five-branch attention in one launch (q pre-scaled by
+ *   D^-1/2 * log2 e).  D = 48 in every format; D = 64 with fmt GP_FMT_BF16 only (the LDS-DMA fast +
+ *   fixup pair at D = 64; GP_FMT_F16 and GP_FMT_F16_VBF16 are rejected there).
+ * gp_branch_merge_ln_varlen: every packed token's LSE merge + inner LN (E = 768, D = 48 or
+ *   E = 1024, D = 64);
  *   out: [T, E] act (the plan's qkv format), row = packed token. */
 int64_t gp_varlen_plan_bytes(int nslide, int nbranch);
 int gp_varlen_plan(const int64_t* L, int nslide, int H, int D, const int32_t* seg_len,

@@ -504,8 +504,11 @@ static_assert(kNWFast == 4 || kNWFast == 8 || kNWFast == 16, "GP_ATTN_NW must be
 // minimum waves per SIMD the kernel instantiation is sized for (HIP launch-bounds semantics; 2: no register
 // constraint at these sizes -- the fixup / exact / register-staged kernels, 104-138 VGPRs)
 // (the 4-wave fast kernel of under-filled launches keeps the interleaved body, no register cap)
-template <int MODE, int NW>
-constexpr int attn_wps() { return MODE == 0 && NW == 8 ? GP_ATTN_FAST_WPS : 2; }
+// D = 64 (the packed launch's fast kernel): 4 = two workgroups per CU.  Its O^T (32), Q (16), S (16) and P (8)
+// registers alone are 72 of the 80 that six waves per SIMD allow -- the one-sub-tile body spilled 51 registers
+// there, inside the tile loop -- so it keeps the interleaved body and the row sum's lane-local adds
+template <int MODE, int NW, int D = 48>
+constexpr int attn_wps() { return MODE == 0 && NW == 8 ? (D == 64 ? 4 : GP_ATTN_FAST_WPS) : 2; }
 // Measured lab variants of this kernel (the 16x16x32 P.V GP_ATTN_PV16, the 3-slot ring GP_ATTN_RING3) build
 // from round 3's source in git (make -C tools/attn_lab r3lab).
 
@@ -519,7 +522,10 @@ __device__ __forceinline__ void attn32_item(const AttnArgs& a, const int item_id
   static_assert(!kH || D == 48 || MODE == kModeGen, "fp16 LDS-DMA modes: D = 48");
   static_assert(!kParts || (MODE != kModeGen && !kTab), "key parts: LDS-DMA modes, branch launches");
   static_assert(D == 48 || D == 64, "v2 kernel covers D = 48 and 64");
-  static_assert(MODE == kModeGen || (D == 48 && kPre), "LDS-DMA modes need D = 48 and a pre-scaled q");
+  static_assert(MODE == kModeGen || kPre, "LDS-DMA modes need a pre-scaled q");
+  static_assert(MODE == kModeGen || D == 48 ||
+                    (kTab && !kH && !kParts && !kList && (MODE == kModeFast || MODE == kModeFix)),
+                "LDS-DMA modes at D = 64: the packed (work-table) bf16 pair");
   static_assert(NW == 4 || ((NW == 8 || NW == 16) && MODE != kModeGen), "8 / 16 waves: LDS-DMA modes only");
   constexpr int NT = NW * 64;
   constexpr int QB = NW * 32;                // query rows per workgroup
@@ -539,9 +545,12 @@ __device__ __forceinline__ void attn32_item(const AttnArgs& a, const int item_id
   constexpr int VTILE = KT * VROWB;
   constexpr int BUF = KTILE + VTILE;
   constexpr int CH = D / 8;                  // 16-byte chunks per K/V row in HBM
+  constexpr int KU = KROWB / 16;             // 16-byte units per K image row: CH data + 1 pad
+  constexpr int VB = D / 16;                 // 32-byte data blocks per V image row (of 4)
   constexpr int TOT = 2 * KT * CH;           // 16-byte chunks of one K tile + one V tile
   constexpr int LPT = (MODE == kModeGen) ? TOT / NT : 1;
   static_assert(MODE != kModeGen || TOT % NT == 0, "");
+  static_assert(MODE == kModeGen || (KTILE % 1024 == 0 && VTILE % 1024 == 0), "K / V images: whole 1-KiB DMA pieces");
   constexpr float kThr = 8.0f;               // lazy-rescale threshold (log2 units)
   constexpr int NBUF = 2;                    // K/V tile buffers (double-buffered)
   __shared__ __attribute__((aligned(16))) char smem[NBUF * BUF];
@@ -634,9 +643,10 @@ __device__ __forceinline__ void attn32_item(const AttnArgs& a, const int item_id
   const uint16_t* lsrc[LPT];
   int lrow[LPT], loff[LPT];
   uint4 stage[LPT];
-  // kDMA: piece p of the 15 (7 K + 8 V) goes to wave p % NW; lane-linear 16-B units.  K image:
-  // 112-B rows = 6 chunks + 1 pad unit (pad lanes off); V image: 128-B rows, swizzled 32-B blocks
-  // (the lanes of the bf16-ones block are off: the prologue wrote it)
+  // kDMA: piece p of the 15 (7 K + 8 V; D = 64: 17 = 9 K + 8 V) goes to wave p % NW; lane-linear 16-B units.
+  // K image: 112-B rows = 6 chunks + 1 pad unit (D = 64: 144-B rows = 8 + 1), pad lanes off; V image: 128-B
+  // rows, swizzled 32-B blocks (D = 48: the lanes of the bf16-ones block are off, the prologue wrote it;
+  // D = 64: all four blocks are data and no V lane is off)
   constexpr int kPieces = (KT * KROWB + KT * VROWB) / 1024;
   constexpr int PPW = (kPieces + NW - 1) / NW;   // pieces per wave
   int dvo[PPW];
@@ -648,14 +658,14 @@ __device__ __forceinline__ void attn32_item(const AttnArgs& a, const int item_id
       dvo[sl] = 0;
       if (pc >= kPieces) continue;
       if (pc < KTILE / 1024) {
-        const int unit = pc * 64 + lane, row = unit / 7, ch = unit % 7;
-        dvo[sl] = (int)((int64_t)row * kvstride * 2 + (ch < 6 ? ch : 0) * 16);
-        if (ch < 6) dmask |= 1u << sl;
+        const int unit = pc * 64 + lane, row = unit / KU, ch = unit % KU;
+        dvo[sl] = (int)((int64_t)row * kvstride * 2 + (ch < CH ? ch : 0) * 16);
+        if (ch < CH) dmask |= 1u << sl;
       } else {
         const int unit = (pc - KTILE / 1024) * 64 + lane, row = unit / 8, slot = unit % 8;
         const int b = (slot >> 1) ^ (row & 3);
-        dvo[sl] = (int)(kv_dv + (int64_t)row * kvstride * 2 + (2 * (b < 3 ? b : 0) + (slot & 1)) * 16);
-        if (b < 3) dmask |= 1u << sl;
+        dvo[sl] = (int)(kv_dv + (int64_t)row * kvstride * 2 + (2 * (b < VB ? b : 0) + (slot & 1)) * 16);
+        if (b < VB) dmask |= 1u << sl;
       }
     }
   } else {
@@ -745,7 +755,7 @@ __device__ __forceinline__ void attn32_item(const AttnArgs& a, const int item_id
   // pair) runs at s_setprio 1 for the whole kernel (MI355X_MICROARCH.md §Two waves per SIMD, item 4) -- but not
   // the fast kernel at three workgroups per CU: with six waves per SIMD arbitration by age alone measured
   // 1.1-1.8 % faster (profiles/r05_occ6b_*, r05_occ6c_*)
-  if constexpr (attn_wps<MODE, NW>() < 6 && NW >= 8) {
+  if constexpr (attn_wps<MODE, NW, D>() < 6 && NW >= 8) {
     if (__builtin_amdgcn_readfirstlane((int)threadIdx.x) >= NT / 2) __builtin_amdgcn_s_setprio(1);
   }
   // one 64-key tile; SET = the tile's LDS buffer when the loop is unrolled by two (kDMA), so the
@@ -760,7 +770,7 @@ __device__ __forceinline__ void attn32_item(const AttnArgs& a, const int item_id
     const int kv0 = t * KT;
     const char* Kb = kDMA ? (const char*)bufc(setc) : smem + (t & 1) * BUF;
     const char* Vb = Kb + KTILE;
-    if constexpr (attn_wps<MODE, NW>() >= 6) {
+    if constexpr (attn_wps<MODE, NW, D>() >= 6) {
       // the fast kernel (GP_ATTN_FAST_WPS): one 32-key sub-tile at a time -- S, exps and P.V of sub-tile u before
       // sub-tile u + 1's S -- so the body fits 80 VGPRs and three workgroups share each CU
       if (wact) {
@@ -1046,7 +1056,7 @@ __device__ __forceinline__ void attn32_item(const AttnArgs& a, const int item_id
 // (kList: the fixup pass is one block per item -- a list launch holds few items)
 template <int D, bool kPre, int MODE, bool kTab = false, int NW = 4, bool kH = false, bool kParts = false,
           bool kList = false>
-__global__ __launch_bounds__(NW * 64, (attn_wps<MODE, NW>())) void dilated_attn32_kernel(const AttnArgs a) {
+__global__ __launch_bounds__(NW * 64, (attn_wps<MODE, NW, D>())) void dilated_attn32_kernel(const AttnArgs a) {
   if constexpr (kList) {
     attn32_item<D, kPre, MODE, kTab, NW, kH, kParts, true>(
         a, MODE == kModeFix ? (int)blockIdx.x : (int)xcd_group(blockIdx.x, gridDim.x));
@@ -1091,15 +1101,66 @@ __global__ __launch_bounds__(NW * 64, (attn_wps<MODE, NW>())) void dilated_attn3
   }
 }
 
+// The D = 64 LDS-DMA pair (the packed, work-table launch): the same items, compiled with the packed fp32 VALU
+// forms (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32) not emitted, as the weight- and data-gradient units are
+// (Makefile, WGRADFLAGS): its row sums and rescales are plain v_add_f32 / v_mul_f32.  A kernel of its own because
+// the feature is per function and every other instantiation keeps its code (routing those through a shared
+// block function moved their SGPR spill counts).  The fixup pass is dilated_attn32_kernel's, table decode only.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define GP_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define GP_NO_PK_F32
+#endif
+template <int MODE, bool kTab, int NW>
+__global__ __launch_bounds__(NW * 64, (attn_wps<MODE, NW, 64>())) GP_NO_PK_F32 void dilated_attn32_d64_kernel(
+    const AttnArgs a) {
+  static_assert(kTab && (MODE == kModeFast || MODE == kModeFix), "");
+  if constexpr (MODE == kModeFix && kFixItems > 1) {
+    constexpr int QB = NW * 32;
+    const int it0 = (int)blockIdx.x * kFixItems;
+    const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
+    constexpr int SLOTS = kFixItems * (QB / 64);
+    constexpr int NV = (SLOTS + NW - 1) / NW;
+    uint32_t vals[NV];
+    bool use[NV];
+#pragma unroll
+    for (int n = 0; n < NV; ++n) {
+      const int sl = w + NW * n;
+      const int it = it0 + sl / (QB / 64), hf = sl % (QB / 64);
+      const bool live = sl < SLOTS && it < a.total_items;
+      WorkItem wi;
+      AttnBranch te;
+      decode_item_tab(a, live ? it : (int)a.total_items - 1, wi, te);
+      const float* lrow = te.lse + ((int64_t)wi.bn * a.H + wi.hh) * te.g.m;
+      const int i = wi.i_lo + wi.qb * QB + 64 * hf + lane;
+      use[n] = live && i < wi.i_hi;
+      vals[n] = __float_as_uint(lrow[use[n] ? i : 0]);
+    }
+    bool flagged = false;
+#pragma unroll
+    for (int n = 0; n < NV; ++n) flagged |= use[n] && vals[n] == kLseRedo;
+    if (!__syncthreads_or(flagged)) return;
+    for (int k = 0; k < kFixItems && it0 + k < a.total_items; ++k) attn32_item<64, true, MODE, kTab, NW, false>(a, it0 + k);
+  } else {
+    attn32_item<64, true, MODE, kTab, NW, false>(
+        a, MODE == kModeFix ? (int)blockIdx.x : (int)xcd_group(blockIdx.x, gridDim.x));
+  }
+}
+
 // The product pair on one stream: the no-max kernel on one block per item, then the fixup pass (exits at once
 // unless a row was flagged) on kFixItems items per block -- one item per block for a query-list launch.
-template <bool kTab, int NW, bool kH, bool kParts = false, bool kList = false>
+template <bool kTab, int NW, bool kH, bool kParts = false, bool kList = false, int D = 48>
 void launch_fast_fix(const AttnArgs& a, hipStream_t s) {
   const int64_t items = a.total_items;
-  dilated_attn32_kernel<48, true, kModeFast, kTab, NW, kH, kParts, kList><<<(unsigned)items, 64 * NW, 0, s>>>(a);
-  if constexpr (GP_ATTN_NOFIX == 0) {
-    const unsigned fix_blocks = (unsigned)(kList ? items : (items + kFixItems - 1) / kFixItems);
-    dilated_attn32_kernel<48, true, kModeFix, kTab, NW, kH, kParts, kList><<<fix_blocks, 64 * NW, 0, s>>>(a);
+  [[maybe_unused]] const unsigned fix_blocks = (unsigned)(kList ? items : (items + kFixItems - 1) / kFixItems);
+  if constexpr (D == 64) {
+    static_assert(!kH && !kParts && !kList, "D = 64: the packed bf16 pair");
+    dilated_attn32_d64_kernel<kModeFast, kTab, NW><<<(unsigned)items, 64 * NW, 0, s>>>(a);
+    if constexpr (GP_ATTN_NOFIX == 0) dilated_attn32_d64_kernel<kModeFix, kTab, NW><<<fix_blocks, 64 * NW, 0, s>>>(a);
+  } else {
+    dilated_attn32_kernel<48, true, kModeFast, kTab, NW, kH, kParts, kList><<<(unsigned)items, 64 * NW, 0, s>>>(a);
+    if constexpr (GP_ATTN_NOFIX == 0)
+      dilated_attn32_kernel<48, true, kModeFix, kTab, NW, kH, kParts, kList><<<fix_blocks, 64 * NW, 0, s>>>(a);
   }
 }
 
@@ -1589,7 +1650,15 @@ extern "C" int gp_dilated_attn_fwd_varlen(const void* plan_host, const void* pla
   GP_REQUIRE(plan_host && plan_dev && gp_aligned(plan_dev, 16), "gp_dilated_attn_fwd_varlen: null/misaligned plan");
   const VarlenHdr h = *static_cast<const VarlenHdr*>(plan_host);
   GP_REQUIRE(h.magic == kVarlenMagic, "gp_dilated_attn_fwd_varlen: not a gp_varlen_plan buffer");
-  GP_REQUIRE(h.D == 48 && q_log2_prescaled, "gp_dilated_attn_fwd_varlen: needs D = 48 and a pre-scaled q (D=%d)", h.D);
+  GP_REQUIRE((h.D == 48 || (h.D == 64 && fmt == GP_FMT_BF16)) && q_log2_prescaled,
+             "gp_dilated_attn_fwd_varlen: needs D = 48, or D = 64 in bf16, and a pre-scaled q (D=%d, fmt=%d)", h.D, fmt);
+  // LDS-DMA staging addresses V as K + dv inside one per-tile buffer descriptor (attn_fwd_impl): 32-bit tile offsets
+  if (h.D == 64) {
+    const AttnBranch* th = reinterpret_cast<const AttnBranch*>(static_cast<const char*>(plan_host) + h.tab_off);
+    for (int x = 0; x < h.ntab; ++x)
+      GP_REQUIRE(4LL * h.H * h.D + 64LL * th[x].g.r * 2 * h.qkv_stride < 0x7fffffff,
+                 "gp_dilated_attn_fwd_varlen: qkv row stride %lld too large for the tile descriptor", (long long)h.qkv_stride);
+  }
   if (h.total_items == 0) return 0;
   AttnArgs a;
   memset(&a, 0, sizeof(a));
@@ -1603,7 +1672,8 @@ extern "C" int gp_dilated_attn_fwd_varlen(const void* plan_host, const void* pla
   a.d_H = make_div_magic((uint32_t)h.H);
   hipStream_t s = gp_stream(stream);
   // the single-slide default's variant, so each packed slide's outputs equal its own launch's
-  if (fmt == GP_FMT_F16)
+  if (h.D == 64) launch_fast_fix<true, kNWFast, false, false, false, 64>(a, s);
+  else if (fmt == GP_FMT_F16)
     dilated_attn32_kernel<48, true, kModeExact, true, kNWFast, true><<<(unsigned)h.total_items, 64 * kNWFast, 0, s>>>(a);
   else if (fmt == GP_FMT_F16_VBF16) launch_fast_fix<true, kNWFast, true>(a, s);
   else launch_fast_fix<true, kNWFast, false>(a, s);

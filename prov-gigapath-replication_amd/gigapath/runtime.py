@@ -551,6 +551,13 @@ class VarlenScratch:
         self.plan.bind(qkv, self.outs, self.lses)
 
 
+def varlen_covers(D: int, act: torch.dtype, grad: bool = False) -> bool:
+    """Whether the packed (varlen) attention kernels cover head dim D in the 16-bit format act: D = 48 in bf16 and
+    fp16, forward and backward; D = 64 in bf16, forward only (its LDS-DMA pair is bf16 only -- the fp16 caller's
+    attention there is the exact kernel, one slide at a time -- and the varlen backward covers D = 48)."""
+    return D == 48 or (D == 64 and act == torch.bfloat16 and not grad)
+
+
 def dilated_attention_core(pa: PackedAttention, qkv: torch.Tensor, B: int, L: int, scratch: AttentionScratch,
                            out: torch.Tensor, inner_ln: bool = True, v_bf16: bool = False):
     """qkv: [B*L, 3E] 16-bit (q | k | v; v_bf16: an fp16 qkv whose V third is bf16, see PackedAttention);
@@ -558,8 +565,9 @@ def dilated_attention_core(pa: PackedAttention, qkv: torch.Tensor, B: int, L: in
     every packed slide in one launch each."""
     E, H, D = pa.E, pa.H, pa.D
     if isinstance(scratch, VarlenScratch):
-        if not pa.prescaled:
-            raise RuntimeError("varlen packing needs the pre-scaled q of D = 48")
+        if not pa.prescaled or not varlen_covers(D, qkv.dtype):
+            raise RuntimeError("varlen packing needs the pre-scaled q of D = 48, or of D = 64 in bf16 "
+                               "(D = %d, %s)" % (D, qkv.dtype))
         with TIMER.span("attn"):
             _hip.dilated_attn_fwd_varlen(scratch.plan, True, v_bf16=v_bf16)
         with TIMER.span("merge"):
@@ -656,7 +664,7 @@ class _DilatedAttentionVarlenGrad(torch.autograd.Function):
 def dilated_attention_grad_varlen(qkv: torch.Tensor, Ls: Sequence[int], H: int, D: int, segs, ratios) -> torch.Tensor:
     """qkv [T, 3E] 16-bit, the slides of lengths Ls packed token-major (q | k | v, q already times D^-0.5 log2 e)
     -> merged [T, E]: every slide's own dilated_attention_grad (its own segment schedule, no attention across
-    slides), with a native backward to qkv.  D = 48, the arch the varlen kernels cover."""
+    slides), with a native backward to qkv.  D = 48, the head dim the varlen backward covers."""
     Ls = [int(x) for x in Ls]
     if D != 48:
         raise ValueError("dilated_attention_grad_varlen: the varlen kernels cover D = 48 (got %d)" % D)

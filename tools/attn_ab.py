@@ -2,9 +2,15 @@
 
     python tools/attn_ab.py --libs prod,tools/attn_lab/liblab_tune1.so [--L 70001] [--rounds 7]
         [--branches all,0,1,2,3,4] [--merge]
+    python tools/attn_ab.py --d64-varlen [--out profiles/attn64_varlen_bench.json]
 
 --merge times gp_branch_merge_ln (the five branches' LSE merge + inner LN of one 70k layer, fed by
 the product attention's outputs) per library instead of the attention launches.
+
+--d64-varlen times the D = 64 packed path in one process, arms interleaved, 2 warm-ups, median of
+7 rounds x 3: the LDS-DMA pair through a one-slide varlen plan against the dense register-staged launch
+(gp_dilated_attn_fwd) on the same rows at L = 70,001 and 256,001, and the C5 32-slide mix through forward_packed
+on the 24L1024d arch against the slides one at a time through forward().
 
 "prod" is the in-tree product library.  Every round times every (library, branch set) pair once
 (HIP events around --iters back-to-back launches on random q/k/v of one layer), so clock drift and
@@ -27,8 +33,74 @@ from gigapath import _hip, runtime  # noqa: E402
 SEGS, RATIOS = [1024, 5792, 32768, 185363, 1048576], [1, 2, 4, 8, 16]
 
 
+PEAK_TFLOPS = 2500.0      # MI355X dense bf16 peak the reports are normalised to
+
+
+def _interleaved(arms, rounds=7, iters=3, warmups=2):
+    """arms: {name: callable}.  Each round times every arm once (HIP events around iters calls) -> {name: [ms]}."""
+    times = {k: [] for k in arms}
+    for rnd in range(warmups + rounds):
+        for name, run in arms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                run()
+            e1.record()
+            torch.cuda.synchronize()
+            if rnd >= warmups:
+                times[name].append(e0.elapsed_time(e1) / iters)
+    return times
+
+
+def _report(part, name, ts, flops=None):
+    med = statistics.median(ts)
+    row = {"part": part, "arm": name, "median_ms": round(med, 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4)}
+    if flops is not None:
+        row["tflops_valid"] = round(flops / med / 1e9, 1)
+        row["pct_of_2.5PF_peak"] = round(100.0 * flops / med / 1e9 / PEAK_TFLOPS, 2)
+    print(json.dumps(row), flush=True)
+    return row
+
+
+def d64_varlen_part(out):
+    import numpy as np
+    from gigapath import batch, slide_encoder
+    H, D = 16, 64
+    E = H * D
+    dev = torch.device("cuda")
+    g = torch.Generator(device="cuda").manual_seed(0)
+    res = []
+    for L in (70001, 256001):
+        qkv = torch.randn(L, 3 * E, device="cuda", generator=g)
+        qkv[:, :E] *= D ** -0.5 * runtime.LOG2E
+        qkv = qkv.to(torch.bfloat16)
+        vs = runtime.VarlenScratch(dev, [L], H, D, SEGS, RATIOS, qkv)
+        sc = runtime.AttentionScratch(dev, 1, L, H, D, SEGS, RATIOS, torch.bfloat16)
+        arms = {"varlen_lds_dma_pair": lambda: _hip.dilated_attn_fwd_varlen(vs.plan, True),
+                "dense_register_staged": lambda: _hip.dilated_attn_fwd(qkv, qkv[:, E:], qkv[:, 2 * E:], 3 * E, 1, L, H, D,
+                                                                       SEGS, RATIOS, sc.outs, sc.lses, 0.0, True)}
+        flops = runtime.attention_valid_flops(L, SEGS, RATIOS, H, D)
+        for name, ts in _interleaved(arms).items():
+            res.append(_report("attention L=%d" % L, name, ts, flops))
+        del vs, sc, qkv
+    sizes = batch.mixed_batch_sizes()
+    model = slide_encoder.create_model("", "gigapath_slide_enc24l1024d", 1536).to(dev).eval()
+    rng = np.random.Generator(np.random.PCG64(5))
+    slides = [(torch.randn(n, 1536, device="cuda", generator=g),
+               torch.from_numpy(rng.integers(0, 1000, (n, 2)).astype(np.float32) * 256.0).to(dev)) for n in sizes]
+    with torch.no_grad():
+        arms = {"forward_packed": lambda: model.forward_packed(slides),
+                "slide_by_slide": lambda: [model(x[None], c[None]) for x, c in slides]}
+        for name, ts in _interleaved(arms, iters=1).items():
+            res.append(_report("C5 32-slide mix (%d tiles), 24L1024d forward" % sum(sizes), name, ts))
+    if out:
+        with open(out, "w") as f:
+            json.dump({"rounds": 7, "iters": 3, "warmups": 2, "batch_iters": 1, "results": res}, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--d64-varlen", action="store_true", help="the D = 64 packed path against the dense launch / per-slide forward")
     ap.add_argument("--libs", default="prod")
     ap.add_argument("--L", type=int, default=70001)
     ap.add_argument("--rounds", type=int, default=7)
@@ -40,6 +112,8 @@ def main():
     ap.add_argument("--vbf16", action="store_true",
                     help="fp16 q / k with a bf16 V third (GP_FMT_F16_VBF16: the fp16 caller's fused-QKV product pair)")
     args = ap.parse_args()
+    if args.d64_varlen:
+        return d64_varlen_part(args.out)
     if args.merge:
         args.branches = "all"
     prod = _hip.load_library()
