@@ -325,9 +325,12 @@ int gp_branch_merge_ln_rows(const uint16_t* const* o_in, const float* const* lse
  *   16-byte aligned device buffer (plan_dev) that stays alive while launches use it.
  * gp_dilated_attn_fwd_varlen: every slide's five-branch attention in one launch (q pre-scaled by
  *   D^-1/2 * log2 e).  D = 48 in every format; D = 64 with fmt GP_FMT_BF16 only (the LDS-DMA fast +
- *   fixup pair at D = 64; GP_FMT_F16 and GP_FMT_F16_VBF16 are rejected there).
- * gp_branch_merge_ln_varlen: every packed token's LSE merge + inner LN (E = 768, D = 48 or
- *   E = 1024, D = 64);
+ *   fixup pair at D = 64; GP_FMT_F16 and GP_FMT_F16_VBF16 are rejected there).  D = 96 with fmt
+ *   GP_FMT_BF16 and q_log2_prescaled = 0 only: its LDS-DMA pair takes the q the 12L1536d arch writes
+ *   (not pre-scaled) and multiplies the fp32 scores by D^-1/2 * log2 e itself; any other fmt, or a
+ *   pre-scaled q, is rejected there before any launch.
+ * gp_branch_merge_ln_varlen: every packed token's LSE merge + inner LN (E = 768, D = 48,
+ *   E = 1024, D = 64 or E = 1536, D = 96);
  *   out: [T, E] act (the plan's qkv format), row = packed token. */
 int64_t gp_varlen_plan_bytes(int nslide, int nbranch);
 int gp_varlen_plan(const int64_t* L, int nslide, int H, int D, const int32_t* seg_len,

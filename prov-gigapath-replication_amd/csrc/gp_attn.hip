@@ -12,7 +12,8 @@
 //     gather is folded into the addressing: sparse row i of (segment n, head h) is token
 //     n*s + i*r + h/(Hp/r);
 //   * D = 48 / 64 (v2 kernel, dilated_attn32_kernel): S^T = K.Q^T and O^T += V^T.P^T with
-//     v_mfma_f32_32x32x16_bf16; D = 96 (dilated_attn_kernel): v_mfma_f32_16x16x32_bf16;
+//     v_mfma_f32_32x32x16_bf16; D = 96 (dilated_attn_kernel): v_mfma_f32_16x16x32_bf16 -- the packed
+//     (varlen) bf16 launch at D = 96 has an LDS-DMA pair of its own (dilated_attn96_kernel);
 //   * the reference's zero-padded keys (dilated_attention.py:85-91, unmasked in flash-attn)
 //     are added analytically at the end: n_pad * exp(0 - max) in the denominator.
 // Every launch configuration is fixed at compile time (no run-time variant switches); measured
@@ -507,8 +508,9 @@ static_assert(kNWFast == 4 || kNWFast == 8 || kNWFast == 16, "GP_ATTN_NW must be
 // D = 64 (the packed launch's fast kernel): 4 = two workgroups per CU.  Its O^T (32), Q (16), S (16) and P (8)
 // registers alone are 72 of the 80 that six waves per SIMD allow -- the one-sub-tile body spilled 51 registers
 // there, inside the tile loop -- so it keeps the interleaved body and the row sum's lane-local adds
+// D = 96 (dilated_attn96_kernel, the packed launch): 4 as well -- 96 registers of O^T, Q, S and P, LDS 2 x 58 KiB
 template <int MODE, int NW, int D = 48>
-constexpr int attn_wps() { return MODE == 0 && NW == 8 ? (D == 64 ? 4 : GP_ATTN_FAST_WPS) : 2; }
+constexpr int attn_wps() { return MODE == 0 && NW == 8 ? (D == 64 || D == 96 ? 4 : GP_ATTN_FAST_WPS) : 2; }
 // Measured lab variants of this kernel (the 16x16x32 P.V GP_ATTN_PV16, the 3-slot ring GP_ATTN_RING3) build
 // from round 3's source in git (make -C tools/attn_lab r3lab).
 
@@ -1147,6 +1149,285 @@ __global__ __launch_bounds__(NW * 64, (attn_wps<MODE, NW, 64>())) GP_NO_PK_F32 v
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// D = 96 (the 12L1536d arch), the packed (work-table) bf16 launch: an LDS-DMA fast + fixup pair of its own
+// (DESIGN §3.16).  Work items, 8 waves x 32 queries, 64-key double-buffered tiles, one barrier per tile, the
+// kLseRedo marker, the analytic zero-pad keys and the flagged-rows-only fixup are attn32_item's.  Its own:
+//   * q is NOT pre-scaled (the dense D = 96 path keeps its weights): the fp32 scores are multiplied by
+//     a.c_log2 = D^-0.5 log2 e before v_exp_f32 -- q is never re-rounded;
+//   * S^T = K.Q^T in 6 k-steps, O^T in three 32-row d-blocks: 12 + 12 v_mfma_f32_32x32x16_bf16 per tile and wave;
+//     every d-block is data, so the row sum is the lane-local add of the unrounded p;
+//   * K image: 208-byte rows = 12 chunks + 1 pad unit (13 is odd: conflict-free ds_read_b128), 13 DMA pieces;
+//     V image: 256-byte rows of eight 32-byte slots, data block b (of 6) of row r at slot b ^ 2 (r & 3) -- a row
+//     spans the whole 256-byte bank row, so the 8 (row & 3, block parity) pairs one transposed read pass meets must
+//     take 8 distinct slots -- 16 DMA pieces, the two spare slots' lanes off; 29 pieces over 8 waves;
+//   * one 32-key sub-tile at a time (one S and one P block live) in both modes: O^T 48 + Q 24 + S 16 + P 8
+//     registers, sized for two workgroups per CU (LDS 2 x 58 KiB);
+//   * the fixup pass keeps the running max in the scaled log2 domain and forms p = exp2(s c - m) with one fma
+//     (lazy rescale, kThr), the arithmetic of kModeGen's unscaled-q branch, per sub-tile.
+template <int MODE>
+__device__ __forceinline__ void attn96_item(const AttnArgs& a, const int item_idx) {
+  static_assert(MODE == kModeFast || MODE == kModeFix, "D = 96: the packed bf16 pair");
+  constexpr bool kFix = MODE == kModeFix;
+  constexpr int D = 96, NW = 8, NT = NW * 64, QB = NW * 32, KT = 64;
+  constexpr int KS = D / 16;                 // k-steps of Q.K^T
+  constexpr int DB = D / 32;                 // 32-row d-blocks of O^T
+  constexpr int CH = D / 8;                  // 16-byte chunks per K/V row in HBM
+  constexpr int KROWB = D * 2 + 16, KU = KROWB / 16;
+  constexpr int VROWB = 256, VB = D / 16;    // V image: 8 slots of 32 bytes per row, VB of them data
+  constexpr int KTILE = KT * KROWB, VTILE = KT * VROWB, BUF = KTILE + VTILE;
+  constexpr int KP = KTILE / 1024, kPieces = BUF / 1024, PPW = (kPieces + NW - 1) / NW;
+  static_assert(KTILE % 1024 == 0 && VTILE % 1024 == 0 && KU % 2 == 1 && PPW <= 32, "");
+  static_assert(2 * 2 * BUF <= 160 * 1024, "two workgroups per CU");
+  constexpr float kThr = 8.0f;
+  __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
+
+  WorkItem wi;
+  AttnBranch te;
+  decode_item_tab(a, item_idx, wi, te);
+  const GpBranch g = te.g;
+  const int hh = wi.hh, c = wi.c, bn = wi.bn;
+  const int rows_needed = wi.i_hi;
+  const int q0 = wi.i_lo + wi.qb * QB;
+  if (q0 >= rows_needed) return;
+  const int qvalid = c < rows_needed ? c : rows_needed;   // rows >= c are zero-padded queries
+  float* const lse_row = te.lse + ((int64_t)bn * a.H + hh) * g.m;
+  bool fixrow = true;                        // kFix: only the rows the fast kernel flagged are rewritten
+  if constexpr (kFix) {
+    const int i = q0 + (int)threadIdx.x;
+    bool flagged = false;
+    if (threadIdx.x < QB && i < rows_needed) flagged = __float_as_uint(lse_row[i]) == kLseRedo;
+    if (!__syncthreads_or(flagged)) return;
+    const int iq = q0 + (int)(threadIdx.x >> 6) * 32 + (int)(threadIdx.x & 31);
+    fixrow = iq < rows_needed && __float_as_uint(lse_row[iq]) == kLseRedo;
+  }
+
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int l32 = lane & 31, h = lane >> 5;
+  const int64_t tok0 = (int64_t)wi.n * g.s + wi.j;
+  const int64_t qstride = (int64_t)g.r * a.q_stride;
+  const int64_t kvstride = (int64_t)g.r * te.kv_stride;
+  const uint16_t* qbase = te.q + tok0 * a.q_stride + hh * D;
+  const uint16_t* kbase = te.k + tok0 * te.kv_stride + hh * D;
+  const uint16_t* vbase = te.v + tok0 * te.kv_stride + hh * D;
+  const float cl2 = a.c_log2;
+
+  // Q fragments (B operand): lane holds Q[q = l32][d = 16ks + 8h .. +7], as the model wrote them
+  bf16x8 qf[KS];
+  {
+    const int i = q0 + w * 32 + l32;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      bf16x8 z = {};
+      if (i < qvalid) z = *reinterpret_cast<const bf16x8*>(qbase + (int64_t)i * qstride + 16 * ks + 8 * h);
+      qf[ks] = z;
+    }
+  }
+
+  // K/V staging: piece p of the 29 (13 K + 16 V) goes to wave p % 8, lane-linear 16-byte units.  K: unit u is
+  // chunk u % 13 of row u / 13, the pad unit's lane off.  V: unit u is half u & 1 of slot (u % 16) >> 1 of row
+  // u / 16; the slot holds data block slot ^ 2 (row & 3), blocks 6 and 7 do not exist and their lanes are off.
+  const int64_t kv_dv = (int64_t)((const char*)vbase - (const char*)kbase);
+  int dvo[PPW];
+  unsigned dmask = 0;
+#pragma unroll
+  for (int sl = 0; sl < PPW; ++sl) {
+    const int pc = w + NW * sl;
+    dvo[sl] = 0;
+    if (pc >= kPieces) continue;
+    if (pc < KP) {
+      const int unit = pc * 64 + lane, row = unit / KU, ch = unit % KU;
+      dvo[sl] = (int)((int64_t)row * kvstride * 2 + (ch < CH ? ch : 0) * 16);
+      if (ch < CH) dmask |= 1u << sl;
+    } else {
+      const int unit = (pc - KP) * 64 + lane, row = unit / 16, s16 = unit % 16;
+      const int b = (s16 >> 1) ^ (2 * (row & 3));
+      dvo[sl] = (int)(kv_dv + (int64_t)row * kvstride * 2 + (2 * (b < VB ? b : 0) + (s16 & 1)) * 16);
+      if (b < VB) dmask |= 1u << sl;
+    }
+  }
+  // the tile's descriptor ends at the last valid key's V row: rows past c read as zero
+  auto load_tile = [&](int kv0, auto bc) {
+    const int64_t tb = (int64_t)kv0 * kvstride * 2;
+    const int64_t nrec = (int64_t)(c - kv0 - 1) * kvstride * 2 + kv_dv + 2 * D;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)((const char*)kbase + tb), (short)0, (int)(nrec < 0x7fffffff ? nrec : 0x7fffffff), 0x00020000);
+    char* bufp = smem + decltype(bc)::value * BUF;
+#pragma unroll
+    for (int sl = 0; sl < PPW; ++sl) {
+      const int pc = w + NW * sl;
+      if (pc < kPieces && ((dmask >> sl) & 1u))
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(bufp + pc * 1024), 16,
+                                                 dvo[sl], 0, 0, 0);
+    }
+  };
+
+  float m_run = kFix ? -INFINITY : 0.f;   // kFix: running max of query l32, scaled log2 domain
+  float lsum = 0.f;
+  f32x16 oacc[DB];
+#pragma unroll
+  for (int mt = 0; mt < DB; ++mt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) oacc[mt][r] = 0.f;
+
+  using S0 = std::integral_constant<int, 0>;
+  using S1 = std::integral_constant<int, 1>;
+  const int ntiles = (c + KT - 1) / KT;
+  if (ntiles > 0) load_tile(0, S0());
+  __builtin_amdgcn_s_waitcnt(0x0f70);   // Q fragments and this wave's pieces of tile 0 (see attn32_item)
+  __syncthreads();
+  if (__builtin_amdgcn_readfirstlane((int)threadIdx.x) >= NT / 2) __builtin_amdgcn_s_setprio(1);
+  const bool wact = __builtin_amdgcn_readfirstlane(q0 + w * 32) < rows_needed;
+  // V^T fragment lane offset of d-block 0 (transposed reads, 8 bytes per lane)
+  const int vlane = (4 * (lane >> 5) + ((lane >> 2) & 3)) * VROWB + 64 * ((lane >> 2) & 3) + 32 * ((lane >> 4) & 1) +
+                    8 * (lane & 3);
+  auto tile_step = [&](int t, auto setc) {
+    constexpr int SET = decltype(setc)::value;
+    if (t + 1 < ntiles) load_tile((t + 1) * KT, std::integral_constant<int, 1 - SET>());
+    const int kv0 = t * KT;
+    const char* Kb = smem + SET * BUF;
+    const char* Vb = Kb + KTILE;
+    if (wact) {
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+          const bf16x8 kk = *reinterpret_cast<const bf16x8*>(Kb + (32 * u + l32) * KROWB + 32 * ks + 16 * h);
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kk, qf[ks], acc, 0, 0, 0);
+        }
+        if (kv0 + 64 > c) {      // keys >= c are zero pads (added analytically at the end)
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (kv0 + 32 * u + (r & 3) + 8 * (r >> 2) + 4 * h >= c) acc[r] = -INFINITY;
+        }
+        if constexpr (kFix) {
+          float mx = acc[0];
+#pragma unroll
+          for (int r = 1; r < 16; ++r) mx = fmaxf(mx, acc[r]);
+          const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
+          const float tm = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1])) * cl2;
+          const bool need = tm > m_run + kThr;   // the first sub-tile: always (m_run = -inf, key 0 is real)
+          if (__builtin_amdgcn_ballot_w64(need)) {
+            const float m_new = need ? tm : m_run;
+            const float alpha = fast_exp2(m_run - m_new);
+#pragma unroll
+            for (int mt = 0; mt < DB; ++mt)
+#pragma unroll
+              for (int r = 0; r < 16; ++r) oacc[mt][r] *= alpha;
+            lsum *= alpha;
+            m_run = m_new;
+          }
+        }
+        bf16x8 pu[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float p = fast_exp2(kFix ? fmaf(acc[8 * s + e], cl2, -m_run) : acc[8 * s + e] * cl2);
+            lsum += p;
+            pu[s][e] = f2e_slot<false>(p);
+          }
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+#pragma unroll
+          for (int mt = 0; mt < DB; ++mt) {
+            // row 32u + 16s + 4 (lane >> 5) + (lane >> 2 & 3), block 2 mt + (lane >> 4 & 1) at slot block ^ 2 (row & 3):
+            // the slot's two high bits are bits 6-7 of vlane and nothing else touches them, so mt is an xor
+            const char* p0 = Vb + (32 * u + 16 * s) * VROWB + (vlane ^ (64 * mt));
+            const char* p1 = p0 + 8 * VROWB;   // rows + 8 keep (row & 3)
+            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);
+            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p1);
+            const bf16x8 vf = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+            oacc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pu[s], oacc[mt], 0, 0, 0);
+          }
+        }
+      }
+    }
+    __builtin_amdgcn_s_waitcnt(0x0f70);   // this wave's DMA pieces landed
+    __syncthreads();
+  };
+  for (int t = 0; t < ntiles; t += 2) {
+    tile_step(t, S0());
+    if (t + 1 < ntiles) tile_step(t + 1, S1());
+  }
+
+  // ---- epilogue: the query's two half sums, range flag, zero-pad keys, normalise, store
+  const auto swl = __builtin_amdgcn_permlane32_swap(__float_as_uint(lsum), __float_as_uint(lsum), false, false);
+  float l = __uint_as_float(swl[0]) + __uint_as_float(swl[1]);
+  const int npad = g.m - c;
+  bool redo = false;
+  if constexpr (!kFix) {   // as attn32_item: with zero-pad keys (p = 1 each) a tiny real-key sum is not flagged
+    const uint32_t eb = __float_as_uint(l) & 0x7f800000u;
+    redo = eb == 0x7f800000u || !(l <= 0x1p100f) || (npad == 0 && !(l >= 0x1p-100f));
+  }
+  float mr = m_run, so = 1.f;
+  if (npad > 0) {
+    const float mf = fmaxf(mr, 0.f);
+    so = fast_exp2(mr - mf);
+    l = l * so + (float)npad * fast_exp2(-mf);
+    mr = mf;
+  }
+  const float inv = so / l;
+  const int i = q0 + w * 32 + l32;
+  // lane (q, h) holds d = 8k + 4h .. +3 of the 12 groups k: one permlane32_swap per dword and pair of groups gives
+  // lanes 0-31 d = 8k .. 8k+7 and lanes 32-63 the next 8 -- six 16-byte stores per 192-byte head row (EXEC full here)
+  uint2 pk[D / 8];
+#pragma unroll
+  for (int k = 0; k < D / 8; ++k) {
+    const int mt = k / 4, rg = k % 4;
+    pk[k].x = (uint32_t)f2e<false>(oacc[mt][4 * rg] * inv) | ((uint32_t)f2e<false>(oacc[mt][4 * rg + 1] * inv) << 16);
+    pk[k].y = (uint32_t)f2e<false>(oacc[mt][4 * rg + 2] * inv) | ((uint32_t)f2e<false>(oacc[mt][4 * rg + 3] * inv) << 16);
+  }
+#pragma unroll
+  for (int k = 0; k < D / 8; k += 2) {
+    const auto rx = __builtin_amdgcn_permlane32_swap(pk[k].x, pk[k + 1].x, false, false);
+    const auto ry = __builtin_amdgcn_permlane32_swap(pk[k].y, pk[k + 1].y, false, false);
+    pk[k].x = rx[0]; pk[k + 1].x = rx[1];
+    pk[k].y = ry[0]; pk[k + 1].y = ry[1];
+  }
+  if (i < rows_needed && fixrow) {
+    uint16_t* orow = te.o + (((int64_t)bn * g.m + i) * a.H + hh) * (int64_t)D + 8 * h;
+#pragma unroll
+    for (int k = 0; k < D / 8; k += 2)
+      *reinterpret_cast<uint4*>(orow + 8 * k) = make_uint4(pk[k].x, pk[k].y, pk[k + 1].x, pk[k + 1].y);
+    const float lse = redo ? __uint_as_float(kLseRedo) : (mr + __builtin_amdgcn_logf(l)) * 0.69314718055994530942f;
+    if (h == 0) lse_row[i] = lse;
+  }
+}
+
+// The pair's kernels, built without the packed fp32 VALU forms like the D = 64 pair.  The fixup pass reads the lse of
+// every needed row of its kFixItems items at once (dilated_attn32_kernel's scan, table decode) and exits unless one
+// holds the marker.
+template <int MODE>
+__global__ __launch_bounds__(512, (attn_wps<MODE, 8, 96>())) GP_NO_PK_F32 void dilated_attn96_kernel(const AttnArgs a) {
+  if constexpr (MODE == kModeFix) {
+    constexpr int NW = 8, QB = NW * 32, SLOTS = kFixItems * (QB / 64), NV = (SLOTS + NW - 1) / NW;
+    const int it0 = (int)blockIdx.x * kFixItems;
+    const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
+    bool flagged = false;
+#pragma unroll
+    for (int n = 0; n < NV; ++n) {
+      const int sl = w + NW * n;
+      const int it = it0 + sl / (QB / 64), hf = sl % (QB / 64);
+      const bool live = sl < SLOTS && it < a.total_items;
+      WorkItem wi;
+      AttnBranch te;
+      decode_item_tab(a, live ? it : (int)a.total_items - 1, wi, te);
+      const float* lrow = te.lse + ((int64_t)wi.bn * a.H + wi.hh) * te.g.m;
+      const int i = wi.i_lo + wi.qb * QB + 64 * hf + lane;
+      const bool use = live && i < wi.i_hi;
+      flagged |= use && __float_as_uint(lrow[use ? i : 0]) == kLseRedo;
+    }
+    if (!__syncthreads_or(flagged)) return;
+    for (int k = 0; k < kFixItems && it0 + k < a.total_items; ++k) attn96_item<MODE>(a, it0 + k);
+  } else {
+    attn96_item<MODE>(a, (int)xcd_group(blockIdx.x, gridDim.x));
+  }
+}
+
 // The product pair on one stream: the no-max kernel on one block per item, then the fixup pass (exits at once
 // unless a row was flagged) on kFixItems items per block -- one item per block for a query-list launch.
 template <bool kTab, int NW, bool kH, bool kParts = false, bool kList = false, int D = 48>
@@ -1650,10 +1931,15 @@ extern "C" int gp_dilated_attn_fwd_varlen(const void* plan_host, const void* pla
   GP_REQUIRE(plan_host && plan_dev && gp_aligned(plan_dev, 16), "gp_dilated_attn_fwd_varlen: null/misaligned plan");
   const VarlenHdr h = *static_cast<const VarlenHdr*>(plan_host);
   GP_REQUIRE(h.magic == kVarlenMagic, "gp_dilated_attn_fwd_varlen: not a gp_varlen_plan buffer");
-  GP_REQUIRE((h.D == 48 || (h.D == 64 && fmt == GP_FMT_BF16)) && q_log2_prescaled,
-             "gp_dilated_attn_fwd_varlen: needs D = 48, or D = 64 in bf16, and a pre-scaled q (D=%d, fmt=%d)", h.D, fmt);
+  if (h.D == 96)   // the D = 96 pair scales the scores itself: the 12L1536d arch's q is not pre-scaled
+    GP_REQUIRE(fmt == GP_FMT_BF16 && !q_log2_prescaled && kNWFast == 8,   // (the plan's 256-query items)
+               "gp_dilated_attn_fwd_varlen: D = 96 needs bf16 and a q that is not pre-scaled (fmt=%d, prescaled=%d)", fmt,
+               q_log2_prescaled);
+  else
+    GP_REQUIRE((h.D == 48 || (h.D == 64 && fmt == GP_FMT_BF16)) && q_log2_prescaled,
+               "gp_dilated_attn_fwd_varlen: needs D = 48, or D = 64 in bf16, and a pre-scaled q (D=%d, fmt=%d)", h.D, fmt);
   // LDS-DMA staging addresses V as K + dv inside one per-tile buffer descriptor (attn_fwd_impl): 32-bit tile offsets
-  if (h.D == 64) {
+  if (h.D == 64 || h.D == 96) {
     const AttnBranch* th = reinterpret_cast<const AttnBranch*>(static_cast<const char*>(plan_host) + h.tab_off);
     for (int x = 0; x < h.ntab; ++x)
       GP_REQUIRE(4LL * h.H * h.D + 64LL * th[x].g.r * 2 * h.qkv_stride < 0x7fffffff,
@@ -1665,14 +1951,19 @@ extern "C" int gp_dilated_attn_fwd_varlen(const void* plan_host, const void* pla
   a.q_stride = h.qkv_stride;
   a.H = h.H;
   a.nbranch = h.nbranch;
-  a.c_log2 = 1.0f;
+  // D = 96: the kernel scales the fp32 scores (gp_dilated_attn_fwd's constant for softmax_scale <= 0)
+  a.c_log2 = h.D == 96 ? (1.0f / sqrtf((float)h.D)) * 1.44269504088896340736f : 1.0f;
   a.total_items = h.total_items;
   a.tab = reinterpret_cast<const AttnBranch*>(static_cast<const char*>(plan_dev) + h.tab_off);
   a.ntab = h.ntab;
   a.d_H = make_div_magic((uint32_t)h.H);
   hipStream_t s = gp_stream(stream);
   // the single-slide default's variant, so each packed slide's outputs equal its own launch's
-  if (h.D == 64) launch_fast_fix<true, kNWFast, false, false, false, 64>(a, s);
+  if (h.D == 96) {
+    dilated_attn96_kernel<kModeFast><<<(unsigned)h.total_items, 512, 0, s>>>(a);
+    if constexpr (GP_ATTN_NOFIX == 0)
+      dilated_attn96_kernel<kModeFix><<<(unsigned)((h.total_items + kFixItems - 1) / kFixItems), 512, 0, s>>>(a);
+  } else if (h.D == 64) launch_fast_fix<true, kNWFast, false, false, false, 64>(a, s);
   else if (fmt == GP_FMT_F16)
     dilated_attn32_kernel<48, true, kModeExact, true, kNWFast, true><<<(unsigned)h.total_items, 64 * kNWFast, 0, s>>>(a);
   else if (fmt == GP_FMT_F16_VBF16) launch_fast_fix<true, kNWFast, true>(a, s);

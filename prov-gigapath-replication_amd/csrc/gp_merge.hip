@@ -768,8 +768,8 @@ extern "C" int gp_branch_merge_ln_varlen(const void* plan_host, const void* plan
   GP_REQUIRE(plan_host && plan_dev && gp_aligned(plan_dev, 16), "gp_branch_merge_ln_varlen: null/misaligned plan");
   const VarlenHdr h = *static_cast<const VarlenHdr*>(plan_host);
   GP_REQUIRE(h.magic == kVarlenMagic, "gp_branch_merge_ln_varlen: not a gp_varlen_plan buffer");
-  GP_REQUIRE((h.H * h.D == 768 && h.D == 48) || (h.H * h.D == 1024 && h.D == 64),
-             "gp_branch_merge_ln_varlen: needs H*D = 768, D = 48 or H*D = 1024, D = 64");
+  GP_REQUIRE((h.H * h.D == 768 && h.D == 48) || (h.H * h.D == 1024 && h.D == 64) || (h.H * h.D == 1536 && h.D == 96),
+             "gp_branch_merge_ln_varlen: needs H*D = 768, D = 48, H*D = 1024, D = 64 or H*D = 1536, D = 96");
   GP_REQUIRE(out && (ln_w == nullptr || ln_b != nullptr), "gp_branch_merge_ln_varlen: bad output / LN arguments");
   MergeArgs a;
   memset(&a, 0, sizeof(a));
@@ -783,10 +783,13 @@ extern "C" int gp_branch_merge_ln_varlen(const void* plan_host, const void* plan
   // are at most 2 L_i, below 4 GiB for any slide the 1000 x 1000 position grid admits)
   const unsigned nb = merge_v2_grid(h.T);
   hipStream_t s = gp_stream(stream);
-  if (h.D == 64) {
-    // E = 1024: the kernel of the [B, L] merge (launch_merge) through the table addressing, one token per wave
+  if (h.D != 48) {
+    // E = 1024 / 1536: the kernel of the [B, L] merge (launch_merge) through the table addressing, one token per wave
     const unsigned nbg = (unsigned)((h.T + 4 * kTPW - 1) / (4 * kTPW));
-    if (fmt == GP_FMT_F16) branch_merge_kernel<16, 64, true, GP_MAX_BRANCHES, true><<<nbg, 256, 0, s>>>(a);
+    if (h.D == 96) {
+      if (fmt == GP_FMT_F16) branch_merge_kernel<24, 96, true, GP_MAX_BRANCHES, true><<<nbg, 256, 0, s>>>(a);
+      else branch_merge_kernel<24, 96, true, GP_MAX_BRANCHES, false><<<nbg, 256, 0, s>>>(a);
+    } else if (fmt == GP_FMT_F16) branch_merge_kernel<16, 64, true, GP_MAX_BRANCHES, true><<<nbg, 256, 0, s>>>(a);
     else branch_merge_kernel<16, 64, true, GP_MAX_BRANCHES, false><<<nbg, 256, 0, s>>>(a);
     return gp_check_launch("gp_branch_merge_ln_varlen");
   }

@@ -554,8 +554,9 @@ class VarlenScratch:
 def varlen_covers(D: int, act: torch.dtype, grad: bool = False) -> bool:
     """Whether the packed (varlen) attention kernels cover head dim D in the 16-bit format act: D = 48 in bf16 and
     fp16, forward and backward; D = 64 in bf16, forward only (its LDS-DMA pair is bf16 only -- the fp16 caller's
-    attention there is the exact kernel, one slide at a time -- and the varlen backward covers D = 48)."""
-    return D == 48 or (D == 64 and act == torch.bfloat16 and not grad)
+    attention there is the exact kernel, one slide at a time -- and the varlen backward covers D = 48); D = 96 in
+    bf16, forward only, likewise (its pair takes the q that is not pre-scaled and scales the scores itself)."""
+    return D == 48 or (D in (64, 96) and act == torch.bfloat16 and not grad)
 
 
 def dilated_attention_core(pa: PackedAttention, qkv: torch.Tensor, B: int, L: int, scratch: AttentionScratch,
@@ -565,11 +566,11 @@ def dilated_attention_core(pa: PackedAttention, qkv: torch.Tensor, B: int, L: in
     every packed slide in one launch each."""
     E, H, D = pa.E, pa.H, pa.D
     if isinstance(scratch, VarlenScratch):
-        if not pa.prescaled or not varlen_covers(D, qkv.dtype):
-            raise RuntimeError("varlen packing needs the pre-scaled q of D = 48, or of D = 64 in bf16 "
-                               "(D = %d, %s)" % (D, qkv.dtype))
+        if pa.prescaled != (D != 96) or not varlen_covers(D, qkv.dtype):
+            raise RuntimeError("varlen packing needs the pre-scaled q of D = 48, or of D = 64 in bf16, or the "
+                               "unscaled q of D = 96 in bf16 (D = %d, %s)" % (D, qkv.dtype))
         with TIMER.span("attn"):
-            _hip.dilated_attn_fwd_varlen(scratch.plan, True, v_bf16=v_bf16)
+            _hip.dilated_attn_fwd_varlen(scratch.plan, pa.prescaled, v_bf16=v_bf16)
         with TIMER.span("merge"):
             _hip.branch_merge_ln_varlen(scratch.plan, pa.ln_w if inner_ln else None, pa.ln_b if inner_ln else None,
                                         pa.ln_eps, out)

@@ -510,7 +510,7 @@ class LongNetViT(nn.Module):
         if not runtime.varlen_covers(self.encoder.layers[0].self_attn.head_dim, runtime.act_dtype(), grad_path) or \
                 len({c.dtype for c in cs}) != 1 or len({x.dtype for x in xs}) != 1:
             # the varlen kernels cover D = 48 (the 12L768d arch) and, for the bf16 inference forward, D = 64
-            # (24L1024d); training and the fp16 caller at D = 64, and the D = 96 arch, run slide by slide
+            # (24L1024d) and D = 96 (12L1536d); training and the fp16 caller at D = 64 / 96 run slide by slide
             return [self.forward(x[None], c[None], all_layer_embed) for x, c in zip(xs, cs)]
         Ns = tuple(int(x.shape[0]) for x in xs)
         x_cat = torch.cat(xs, 0)

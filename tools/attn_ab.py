@@ -3,6 +3,7 @@
     python tools/attn_ab.py --libs prod,tools/attn_lab/liblab_tune1.so [--L 70001] [--rounds 7]
         [--branches all,0,1,2,3,4] [--merge]
     python tools/attn_ab.py --d64-varlen [--out profiles/attn64_varlen_bench.json]
+    python tools/attn_ab.py --d96-varlen [--out profiles/attn96_varlen_bench.json]
 
 --merge times gp_branch_merge_ln (the five branches' LSE merge + inner LN of one 70k layer, fed by
 the product attention's outputs) per library instead of the attention launches.
@@ -10,7 +11,9 @@ the product attention's outputs) per library instead of the attention launches.
 --d64-varlen times the D = 64 packed path in one process, arms interleaved, 2 warm-ups, median of
 7 rounds x 3: the LDS-DMA pair through a one-slide varlen plan against the dense register-staged launch
 (gp_dilated_attn_fwd) on the same rows at L = 70,001 and 256,001, and the C5 32-slide mix through forward_packed
-on the 24L1024d arch against the slides one at a time through forward().
+on the 24L1024d arch against the slides one at a time through forward().  --d96-varlen is the same protocol for
+the D = 96 pair: q not pre-scaled, the dense arm is dilated_attn_kernel<96>, the batch arms run the
+12L1536d arch.
 
 "prod" is the in-tree product library.  Every round times every (library, branch set) pair once
 (HIP events around --iters back-to-back launches on random q/k/v of one layer), so clock drift and
@@ -62,29 +65,30 @@ def _report(part, name, ts, flops=None):
     return row
 
 
-def d64_varlen_part(out):
+def varlen_part(out, D, arch):
     import numpy as np
     from gigapath import batch, slide_encoder
-    H, D = 16, 64
+    H, pre = 16, D != 96
     E = H * D
     dev = torch.device("cuda")
     g = torch.Generator(device="cuda").manual_seed(0)
     res = []
     for L in (70001, 256001):
         qkv = torch.randn(L, 3 * E, device="cuda", generator=g)
-        qkv[:, :E] *= D ** -0.5 * runtime.LOG2E
+        if pre:
+            qkv[:, :E] *= D ** -0.5 * runtime.LOG2E
         qkv = qkv.to(torch.bfloat16)
         vs = runtime.VarlenScratch(dev, [L], H, D, SEGS, RATIOS, qkv)
         sc = runtime.AttentionScratch(dev, 1, L, H, D, SEGS, RATIOS, torch.bfloat16)
-        arms = {"varlen_lds_dma_pair": lambda: _hip.dilated_attn_fwd_varlen(vs.plan, True),
+        arms = {"varlen_lds_dma_pair": lambda: _hip.dilated_attn_fwd_varlen(vs.plan, pre),
                 "dense_register_staged": lambda: _hip.dilated_attn_fwd(qkv, qkv[:, E:], qkv[:, 2 * E:], 3 * E, 1, L, H, D,
-                                                                       SEGS, RATIOS, sc.outs, sc.lses, 0.0, True)}
+                                                                       SEGS, RATIOS, sc.outs, sc.lses, 0.0, pre)}
         flops = runtime.attention_valid_flops(L, SEGS, RATIOS, H, D)
         for name, ts in _interleaved(arms).items():
             res.append(_report("attention L=%d" % L, name, ts, flops))
         del vs, sc, qkv
     sizes = batch.mixed_batch_sizes()
-    model = slide_encoder.create_model("", "gigapath_slide_enc24l1024d", 1536).to(dev).eval()
+    model = slide_encoder.create_model("", arch, 1536).to(dev).eval()
     rng = np.random.Generator(np.random.PCG64(5))
     slides = [(torch.randn(n, 1536, device="cuda", generator=g),
                torch.from_numpy(rng.integers(0, 1000, (n, 2)).astype(np.float32) * 256.0).to(dev)) for n in sizes]
@@ -92,7 +96,8 @@ def d64_varlen_part(out):
         arms = {"forward_packed": lambda: model.forward_packed(slides),
                 "slide_by_slide": lambda: [model(x[None], c[None]) for x, c in slides]}
         for name, ts in _interleaved(arms, iters=1).items():
-            res.append(_report("C5 32-slide mix (%d tiles), 24L1024d forward" % sum(sizes), name, ts))
+            res.append(_report("C5 32-slide mix (%d tiles), %s forward" % (sum(sizes), arch[-8:].upper().replace("D", "d")),
+                               name, ts))
     if out:
         with open(out, "w") as f:
             json.dump({"rounds": 7, "iters": 3, "warmups": 2, "batch_iters": 1, "results": res}, f, indent=1)
@@ -101,6 +106,7 @@ def d64_varlen_part(out):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--d64-varlen", action="store_true", help="the D = 64 packed path against the dense launch / per-slide forward")
+    ap.add_argument("--d96-varlen", action="store_true", help="the same for the D = 96 pair and the 12L1536d arch")
     ap.add_argument("--libs", default="prod")
     ap.add_argument("--L", type=int, default=70001)
     ap.add_argument("--rounds", type=int, default=7)
@@ -113,7 +119,9 @@ def main():
                     help="fp16 q / k with a bf16 V third (GP_FMT_F16_VBF16: the fp16 caller's fused-QKV product pair)")
     args = ap.parse_args()
     if args.d64_varlen:
-        return d64_varlen_part(args.out)
+        return varlen_part(args.out, 64, "gigapath_slide_enc24l1024d")
+    if args.d96_varlen:
+        return varlen_part(args.out, 96, "gigapath_slide_enc12l1536d")
     if args.merge:
         args.branches = "all"
     prod = _hip.load_library()
