@@ -299,6 +299,30 @@ int gp_attn_rows_plan(const uint16_t* q, const uint16_t* k, const uint16_t* v, i
 int gp_dilated_attn_fwd_rows(const void* plan_host, const void* plan_dev, int q_log2_prescaled, int fmt,
                              void* stream);
 
+/* The query-list plan of packed slides (additive to ABI 13): every slide of a gp_varlen_plan pack has its own
+ * L[i], so its own segment schedule and its own lists.  Replaces: gp_attn_rows_plan's one (B, L) and one set of
+ * lists "for all B batches"; the launch is gp_dilated_attn_fwd_rows (same constraints).
+ * L / nslide / H / D / seg_len / ratios / nbranch / qkv / qkv_row_stride / o_out / lse_out as gp_varlen_plan's (the
+ * packed per-branch buffers it sizes: o / lse of (slide, branch) in slide-major regions).  D = 48 only.
+ * Lists, per branch b: grp_off[b] is a HOST int32 array, slide-major: the groups of slide i start at
+ * sum_{i' < i} nseg_i'b r_b and group (n, j) of the slide lies n r_b + j after that; it holds
+ * sum_i nseg_ib r_b + 1 offsets into grp_rows[b], a DEVICE int32 array of the concatenated ascending sparse rows
+ * (each 0 <= row < m_ib).  A slide may have all-empty lists.
+ * One entry per (slide, branch, segment, head group) with a non-empty list carries that slide's geometry
+ * (s = min(sl, L[i]), m, nseg), its first q | k | v row (tok_off[i]), L[i] and its o / lse regions: every row
+ * limit of the kernel (valid keys, the tail segment, the zero-pad keys) is the slide's own and no row of a
+ * neighbouring slide is read.  o / lse of a listed row land where gp_dilated_attn_fwd_varlen writes them, with
+ * the same bits; unlisted rows are not written; the fixup pass covers listed rows.  Entries are ordered by keys
+ * per item, longest first, across all slides.  gp_attn_rows_plan_varlen_bytes: the host buffer's size (-1 on
+ * bad arguments).  Argument errors (null / misaligned pointers, D != 48, list offsets that descend or exceed m,
+ * a plan buffer that is too small) are rejected on the host. */
+int64_t gp_attn_rows_plan_varlen_bytes(const int64_t* L, int nslide, const int32_t* seg_len, const int32_t* ratios,
+                                       int nbranch);
+int gp_attn_rows_plan_varlen(const int64_t* L, int nslide, int H, int D, const int32_t* seg_len,
+                             const int32_t* ratios, int nbranch, const uint16_t* qkv, int64_t qkv_row_stride,
+                             const int32_t* const* grp_off, const int32_t* const* grp_rows,
+                             uint16_t* const* o_out, float* const* lse_out, void* plan_host, int64_t plan_bytes);
+
 /* gp_branch_merge_ln for a list of tokens (ABI 12): out row b*n_rows + k is the merge (+ inner LN) of token
  * rows[k] of batch b, bit-identical to row b*L + rows[k] of gp_branch_merge_ln's output.  rows: [n_rows] int32
  * DEVICE array of tokens in [0, L) (any order; one list for every batch).  out: [B*n_rows, H*D] act, 16-byte
@@ -341,6 +365,19 @@ int gp_dilated_attn_fwd_varlen(const void* plan_host, const void* plan_dev, int 
                                int fmt, void* stream);
 int gp_branch_merge_ln_varlen(const void* plan_host, const void* plan_dev, const float* ln_w,
                               const float* ln_b, float eps, uint16_t* out, int fmt, void* stream);
+
+/* gp_branch_merge_ln_varlen for a list of packed tokens (additive to ABI 13).  Replaces: gp_branch_merge_ln_rows'
+ * one rows list "for every batch" and one L.  plan_host / plan_dev: the gp_varlen_plan buffer, as
+ * gp_branch_merge_ln_varlen takes it.  rows: [n_rows] int32 DEVICE array of PACKED token indices
+ * (tok_off[i] + t), ascending.  out[k] is the merge (+ inner LN) of packed token rows[k], bit-identical to row
+ * rows[k] of gp_branch_merge_ln_varlen's output: a slot's slide is found from its packed token and that slide's
+ * own (s, m, nseg) per branch decide which sparse row and heads cover it.  out: [n_rows, H*D] in fmt
+ * (GP_FMT_BF16 / GP_FMT_F16), 16-byte aligned.  H = 16, D = 48, nbranch = 5 only, as gp_branch_merge_ln_rows;
+ * anything else is rejected on the host before any launch.  With ln_w == NULL nothing but the branch buffers,
+ * the plan and the list is read. */
+int gp_branch_merge_ln_rows_varlen(const void* plan_host, const void* plan_dev, const int32_t* rows,
+                                   int64_t n_rows, const float* ln_w, const float* ln_b, float eps, uint16_t* out,
+                                   int fmt, void* stream);
 
 /* ---- Backward of the packed attention (additive to ABI 13): (dq, dk, dv) of gp_dilated_attn_fwd_varlen + the
  * no-LN gp_branch_merge_ln_varlen with respect to the packed q | k | v, given dmerged [T, H*D].  Per slide it is
@@ -426,6 +463,20 @@ int gp_cls_attn_merge_ln_map(const uint16_t* q, const uint16_t* k, const uint16_
                              const int32_t* ratios, int nbranch, float softmax_scale, int q_log2_prescaled,
                              int fmt, const float* ln_w, const float* ln_b, float eps, uint16_t* out, void* ws,
                              int64_t ws_bytes, void* stream);
+
+/* gp_cls_attn_merge_ln_map with one row map per slide (additive to ABI 13).  Replaces: its one row_map of
+ * [max_len] "for every slide".  row_map: one concatenated int32 DEVICE array; map_off: [nslide] int64 DEVICE
+ * array, slide i's map starts at row_map + map_off[i] and holds slide_len[i] entries.  Token t of slide i lives
+ * at compact row slide_off[i] + row_map[map_off[i] + t]; only the entries of the CLS query's keys are read, and
+ * token 0 maps to row 0.  map_rows: the rows of the WHOLE compact buffer (a row a bad map names is held inside
+ * it).  D = 48 only.  The arithmetic and its order are unchanged: the bits of the unmapped call on the scattered
+ * buffer. */
+int gp_cls_attn_merge_ln_maps(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t row_stride,
+                              const int64_t* slide_off, const int64_t* slide_len, int64_t nslide, int64_t max_len,
+                              const int32_t* row_map, const int64_t* map_off, int64_t map_rows, int H, int D,
+                              const int32_t* seg_len, const int32_t* ratios, int nbranch, float softmax_scale,
+                              int q_log2_prescaled, int fmt, const float* ln_w, const float* ln_b, float eps,
+                              uint16_t* out, void* ws, int64_t ws_bytes, void* stream);
 
 /* Residual add fused with the next pre-LN (encoder.py:141,147 / :159,126):
  *   x += y + bias (fp32 residual stream, in place);  ln_out = LayerNorm(x) (skipped if ln_w == NULL).

@@ -72,9 +72,12 @@ struct AttnArgs {
   const struct AttnListEntry* ltab; // query-list launch (kList): ntab entries in device memory
 };
 
-// Query-list launch (gp_dilated_attn_fwd_rows): one entry per (batch, branch, segment, head group) that has
-// listed rows.  Its work items are (covered head, block of QB list slots); slot k of the entry is sparse row
-// rows[k] of the segment.  br: the branch as a launch holds it, with nqb / d_nqb / item_begin of THIS entry.
+// Query-list launch (gp_dilated_attn_fwd_rows): one entry per (batch or packed slide, branch, segment, head group)
+// that has listed rows.  Its work items are (covered head, block of QB list slots); slot k of the entry is sparse
+// row rows[k] of the segment.  br: the branch as a launch holds it, with nqb / d_nqb / item_begin of THIS entry and
+// the entry's own q and L -- a [B, L] plan stores the batch's q and L in every entry, a packed plan
+// (gp_attn_rows_plan_varlen) each slide's first row, length and o / lse regions with bidx = 0, so every row limit
+// the kernel derives (valid keys, tail segment, zero-pad keys) is the slide's own.
 struct AttnListEntry {
   AttnBranch br;
   const int32_t* rows;   // [count] ascending sparse rows (device)
@@ -179,7 +182,7 @@ GP_DEV void decode_item_list(const AttnArgs& a, int item, WorkItem& w, AttnBranc
   w.n = le.n;
   w.bn = le.bidx * g.nseg + le.n;
   w.j = le.j;
-  const int rem = (int)(a.L - (int64_t)w.n * g.s);
+  const int rem = (int)(e.L - (int64_t)w.n * g.s);
   const int lim = (rem < g.s ? rem : g.s) - w.j;
   w.c = lim > 0 ? (int)div_magic((uint32_t)(lim + g.r - 1), e.d_r) : 0;
   w.i_lo = 0;
@@ -603,12 +606,13 @@ __device__ __forceinline__ void attn32_item(const AttnArgs& a, const int item_id
 
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int l32 = lane & 31, h = lane >> 5;
-  const int64_t tok0 = (int64_t)wi.bidx * a.L + (int64_t)wi.n * g.s + wi.j;
+  // (kList: the batch length and the q base are the entry's -- a packed slide's own)
+  const int64_t tok0 = (int64_t)wi.bidx * (kList ? brr.L : a.L) + (int64_t)wi.n * g.s + wi.j;
   const int64_t qstride = (int64_t)g.r * a.q_stride;
   const int64_t kvstride = (int64_t)g.r * brr.kv_stride;
   const int kcol = brr.kv_sparse ? (hh % g.hpg) * D : hh * D;
-  const uint16_t* qbase = kTab ? brr.q + tok0 * a.q_stride + hh * D
-                               : a.q + (tok0 - a.q_tok_base) * a.q_stride + hh * D;
+  const uint16_t* qbase = (kTab || kList) ? brr.q + tok0 * a.q_stride + hh * D
+                                          : a.q + (tok0 - a.q_tok_base) * a.q_stride + hh * D;
   const uint16_t* kbase = brr.k + (tok0 - brr.kv_tok_base) * brr.kv_stride + kcol;
   const uint16_t* vbase = brr.v + (tok0 - brr.kv_tok_base) * brr.kv_stride + kcol;
 
@@ -1667,6 +1671,8 @@ extern "C" int gp_dilated_attn_fwd(const uint16_t* q, const uint16_t* k, const u
 // Query-list launch (ABI 12): the product attention for listed sparse rows only.  The plan (host bytes, copied
 // by the caller to device memory, as the varlen plan) holds one AttnListEntry per (batch, branch, segment, head
 // group) with a non-empty list, branches ordered by keys per item (longest first); one launch covers them all.
+// Two builders write it: gp_attn_rows_plan (a [B, L] batch, one set of lists) and gp_attn_rows_plan_varlen (packed
+// slides, each with its own lists); the launch reads q, L and the batch index from the entries alone.
 namespace {
 constexpr int32_t kRowsMagic = 0x47505231;   // "GPR1"
 struct RowsHdr {
@@ -1763,13 +1769,123 @@ extern "C" int gp_attn_rows_plan(const uint16_t* q, const uint16_t* k, const uin
   return 0;
 }
 
+// The packed-slide plan: the lists of every slide, each entry with that slide's geometry, rows and regions (the
+// o / lse region of (slide, branch) lies where gp_varlen_plan puts it: slide-major, in slide order).
+extern "C" int64_t gp_attn_rows_plan_varlen_bytes(const int64_t* L, int nslide, const int32_t* seg_len,
+                                                  const int32_t* ratios, int nbranch) {
+  if (!L || nslide < 1 || !seg_len || !ratios || nbranch < 1 || nbranch > GP_MAX_BRANCHES) return -1;
+  int64_t ent = 0;
+  for (int i = 0; i < nslide; ++i)
+    for (int b = 0; b < nbranch; ++b) {
+      if (L[i] < 1 || seg_len[b] < 1 || ratios[b] < 1) return -1;
+      const GpBranch g = gp_make_branch(L[i], seg_len[b], ratios[b], 1);
+      ent += (int64_t)g.nseg * g.r;
+    }
+  return kRowsTabOff + ent * (int64_t)sizeof(AttnListEntry);
+}
+
+extern "C" int gp_attn_rows_plan_varlen(const int64_t* L, int nslide, int H, int D, const int32_t* seg_len,
+                                        const int32_t* ratios, int nbranch, const uint16_t* qkv,
+                                        int64_t qkv_row_stride, const int32_t* const* grp_off,
+                                        const int32_t* const* grp_rows, uint16_t* const* o_out,
+                                        float* const* lse_out, void* plan_host, int64_t plan_bytes) {
+  GP_REQUIRE(D == 48, "gp_attn_rows_plan_varlen: head dim %d unsupported (48)", D);
+  GP_REQUIRE(L && seg_len && ratios && qkv && grp_off && grp_rows && o_out && lse_out && plan_host,
+             "gp_attn_rows_plan_varlen: null pointer");
+  GP_REQUIRE(nslide >= 1 && H > 0 && nbranch >= 1 && nbranch <= GP_MAX_BRANCHES &&
+                 qkv_row_stride >= 3LL * H * D && qkv_row_stride % 8 == 0, "gp_attn_rows_plan_varlen: bad sizes");
+  GP_REQUIRE(gp_aligned(qkv, 16), "gp_attn_rows_plan_varlen: qkv must be 16-byte aligned");
+  const int64_t need = gp_attn_rows_plan_varlen_bytes(L, nslide, seg_len, ratios, nbranch);
+  GP_REQUIRE(need > 0, "gp_attn_rows_plan_varlen: a slide length, segment length or ratio below 1");
+  GP_REQUIRE(plan_bytes >= need, "gp_attn_rows_plan_varlen: plan buffer of %lld bytes, %lld needed",
+             (long long)plan_bytes, (long long)need);
+  std::vector<int64_t> tok_off((size_t)nslide + 1, 0);
+  for (int i = 0; i < nslide; ++i) tok_off[i + 1] = tok_off[i] + L[i];
+  GP_REQUIRE(tok_off[nslide] < (int64_t)0x7fffffff, "gp_attn_rows_plan_varlen: %lld packed tokens is too many",
+             (long long)tok_off[nslide]);
+  const int E = H * D;
+  // LDS-DMA staging (attn_fwd_impl): V addressed as K + dv inside one buffer descriptor, dv = one E-wide third
+  for (int b = 0; b < nbranch; ++b) {
+    GP_REQUIRE(grp_off[b] && grp_rows[b] && o_out[b] && lse_out[b] && gp_aligned(o_out[b], 8),
+               "gp_attn_rows_plan_varlen: bad branch %d", b);
+    GP_REQUIRE(2LL * E + 64 * (int64_t)ratios[b] * 2 * qkv_row_stride < 0x7fffffff,
+               "gp_attn_rows_plan_varlen: qkv row stride %lld too large for the tile descriptor",
+               (long long)qkv_row_stride);
+  }
+  // per (slide, branch): geometry, o / lse region (gp_varlen_plan's), first group of the slide in grp_off[b]
+  const size_t np = (size_t)nslide * nbranch;
+  std::vector<GpBranch> geo(np);
+  std::vector<int64_t> ooff(np), loff(np), goff(np);
+  int64_t oacc[GP_MAX_BRANCHES] = {0}, lacc[GP_MAX_BRANCHES] = {0}, gacc[GP_MAX_BRANCHES] = {0};
+  for (int i = 0; i < nslide; ++i)
+    for (int b = 0; b < nbranch; ++b) {
+      const size_t id = (size_t)i * nbranch + b;
+      const GpBranch g = gp_make_branch(L[i], seg_len[b], ratios[b], H);
+      geo[id] = g;
+      ooff[id] = oacc[b]; loff[id] = lacc[b]; goff[id] = gacc[b];
+      oacc[b] += (int64_t)g.nseg * g.m * H * D;
+      lacc[b] += (int64_t)g.nseg * H * g.m;
+      gacc[b] += (int64_t)g.nseg * g.r;
+    }
+  // entries by keys per item, longest first, across all slides (stable, as gp_varlen_plan orders its table)
+  std::vector<int> order(np);
+  for (size_t x = 0; x < np; ++x) order[x] = (int)x;
+  std::stable_sort(order.begin(), order.end(), [&](int u, int v) { return geo[u].m > geo[v].m; });
+  const int qblk = 32 * kNWFast;
+  AttnListEntry* tab = reinterpret_cast<AttnListEntry*>(static_cast<char*>(plan_host) + kRowsTabOff);
+  int64_t items = 0, nent = 0;
+  for (size_t x = 0; x < np; ++x) {
+    const int id = order[x], i = id / nbranch, b = id % nbranch;
+    const GpBranch& g = geo[id];
+    const int32_t* off = grp_off[b] + goff[id];
+    const uint16_t* row0 = qkv + tok_off[i] * qkv_row_stride;
+    for (int n = 0; n < g.nseg; ++n)
+      for (int j = 0; j < g.r; ++j) {
+        const int32_t lo = off[n * g.r + j], hi = off[n * g.r + j + 1];
+        GP_REQUIRE(lo >= 0 && hi >= lo && hi - lo <= g.m,
+                   "gp_attn_rows_plan_varlen: bad list offsets (slide %d, branch %d)", i, b);
+        const int nheads = std::min(g.hpg, H - j * g.hpg);
+        if (hi == lo || nheads <= 0) continue;
+        AttnListEntry le;
+        memset(&le, 0, sizeof(le));
+        AttnBranch& e = le.br;
+        e.g = g;
+        e.nqb = (hi - lo + qblk - 1) / qblk;
+        e.n_lo = 0;
+        e.nseg_w = g.nseg;
+        e.kv_sparse = 0;
+        e.item_begin = items;
+        e.q = row0; e.k = row0 + E; e.v = row0 + 2 * E;
+        e.kv_stride = qkv_row_stride;
+        e.kv_tok_base = 0;
+        e.o = o_out[b] + ooff[id]; e.lse = lse_out[b] + loff[id];
+        e.kpart = 0; e.kparts = 1;
+        e.L = L[i];
+        attn_branch_magic(e);
+        le.rows = grp_rows[b] + lo;
+        le.count = hi - lo;
+        le.n = n; le.j = j; le.bidx = 0;
+        le.h0 = j * g.hpg;
+        tab[nent++] = le;
+        items += (int64_t)nheads * e.nqb;
+      }
+  }
+  GP_REQUIRE(items < (int64_t)0x7fffffff, "gp_attn_rows_plan_varlen: too many work items");
+  RowsHdr h;
+  memset(&h, 0, sizeof(h));
+  h.magic = kRowsMagic; h.nent = (int32_t)nent; h.H = H; h.D = D;
+  h.L = tok_off[nslide]; h.total_items = items; h.q_stride = qkv_row_stride; h.q = qkv;
+  memcpy(plan_host, &h, sizeof(h));
+  return 0;
+}
+
 extern "C" int gp_dilated_attn_fwd_rows(const void* plan_host, const void* plan_dev, int q_log2_prescaled, int fmt,
                                         void* stream) {
   GP_REQUIRE(fmt == GP_FMT_BF16 || fmt == GP_FMT_F16_VBF16,
              "gp_dilated_attn_fwd_rows: fmt %d unsupported (the bf16 and fp16 / bf16-V pairs)", fmt);
   GP_REQUIRE(plan_host && plan_dev && gp_aligned(plan_dev, 16), "gp_dilated_attn_fwd_rows: null/misaligned plan");
   const RowsHdr h = *static_cast<const RowsHdr*>(plan_host);
-  GP_REQUIRE(h.magic == kRowsMagic, "gp_dilated_attn_fwd_rows: not a gp_attn_rows_plan buffer");
+  GP_REQUIRE(h.magic == kRowsMagic, "gp_dilated_attn_fwd_rows: not a gp_attn_rows_plan / _varlen buffer");
   GP_REQUIRE(h.D == 48 && q_log2_prescaled, "gp_dilated_attn_fwd_rows: needs D = 48 and a pre-scaled q");
   if (h.total_items == 0) return 0;
   AttnArgs a;

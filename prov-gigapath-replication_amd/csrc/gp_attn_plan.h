@@ -42,8 +42,8 @@ struct AttnBranch {
   uint16_t* o;          // [B*nseg, m, H, D]
   float* lse;           // [B*nseg, H, m]
   int32_t kpart, kparts;   // key part kpart of kparts (<= 1: all keys; see GpAttnBranch.key_parts)
-  // varlen table entries only (one per (slide, branch); B = 1, window = the whole slide)
-  const uint16_t* q;    // the slide's first query row
+  // varlen table entries (one per (slide, branch); B = 1, window = the whole slide) and query-list entries
+  const uint16_t* q;    // the slide's (list entry of a [B, L] batch: the batch's) first query row
   int64_t L;            // the slide's length (CLS + tiles)
   DivMagic d_nqb, d_nsegw, d_hpg, d_r;   // the work-item decode's divisors (scalar multiply-high)
 };

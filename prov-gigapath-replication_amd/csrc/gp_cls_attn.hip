@@ -46,6 +46,9 @@ struct ClsArgs {
   // slide holds map_rows rows; NULL: at row slide_off + t
   const int32_t* row_map;
   int32_t map_rows;
+  // one map per slide (gp_cls_attn_merge_ln_maps, kMaps): slide i's map is row_map + map_off[i] and map_rows is
+  // the row count of the whole compact buffer
+  const int64_t* map_off;
 };
 
 // sparse rows (= keys of the CLS query) of branch b at slide length L
@@ -68,9 +71,11 @@ GP_DEV void unpack8(const uint4 u, float* out) {        // 8 16-bit values of on
   }
 }
 
-// kQK / kV: q and k / v are fp16 (else bf16)
-template <int D, bool kQK, bool kV>
-__global__ __launch_bounds__(kChunk) void cls_attn_partial_kernel(const ClsArgs a) {
+// kQK / kV: q and k / v are fp16 (else bf16).  kMaps: the key's row comes from the slide's own map -- the lengths
+// that bound the key index (cls_len, cls_keys) are already per slide, so the map entry read is always one of the
+// slide's own tokens; the row it names is held inside the compact buffer whatever the map says.
+template <int D, bool kQK, bool kV, bool kMaps>
+__device__ __forceinline__ void cls_attn_partial(const ClsArgs& a) {
   __shared__ float red[4][D + 2];
   const int slide = blockIdx.y;
   int item = blockIdx.x, b = 0;
@@ -86,11 +91,17 @@ __global__ __launch_bounds__(kChunk) void cls_attn_partial_kernel(const ClsArgs 
   const bool valid = k0 + tid < m;
   const int64_t tok0 = a.slide_off[slide];
   int64_t trow = valid ? (int64_t)(k0 + tid) * a.r[b] : 0;
-  if (a.row_map != nullptr) {                            // (held inside the slide's rows whatever the map says)
-    const int32_t mr = a.row_map[trow];
-    trow = mr < 0 ? 0 : (mr < a.map_rows ? mr : a.map_rows - 1);
+  int64_t tok;
+  if constexpr (kMaps) {
+    const int64_t row = tok0 + a.row_map[a.map_off[slide] + trow];
+    tok = row < 0 ? 0 : (row < a.map_rows ? row : (int64_t)a.map_rows - 1);
+  } else {
+    if (a.row_map != nullptr) {                          // (held inside the slide's rows whatever the map says)
+      const int32_t mr = a.row_map[trow];
+      trow = mr < 0 ? 0 : (mr < a.map_rows ? mr : a.map_rows - 1);
+    }
+    tok = tok0 + trow;
   }
-  const int64_t tok = tok0 + trow;
   // the key's k and v rows (D 16-bit values each, 16-byte accesses), all in flight before the first use
   const uint4* kp = reinterpret_cast<const uint4*>(a.k + tok * a.row_stride + h * D);
   const uint4* vp = reinterpret_cast<const uint4*>(a.v + tok * a.row_stride + h * D);
@@ -132,6 +143,16 @@ __global__ __launch_bounds__(kChunk) void cls_attn_partial_kernel(const ClsArgs 
   if (tid < D) rec[kRecHead + tid] = (red[0][2 + tid] + red[1][2 + tid]) + (red[2][2 + tid] + red[3][2 + tid]);
   if (tid == D) rec[0] = mx;
   if (tid == D + 1) rec[1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+}
+
+template <int D, bool kQK, bool kV>
+__global__ __launch_bounds__(kChunk) void cls_attn_partial_kernel(const ClsArgs a) {
+  cls_attn_partial<D, kQK, kV, false>(a);
+}
+// gp_cls_attn_merge_ln_maps (D = 48)
+template <bool kQK, bool kV>
+__global__ __launch_bounds__(kChunk) void cls_attn_partial_maps_kernel(const ClsArgs a) {
+  cls_attn_partial<48, kQK, kV, true>(a);
 }
 
 constexpr int kMergeWaves = 16;    // waves of the per-slide workgroup: one (branch, head) each per round
@@ -295,6 +316,62 @@ void launch_partial(const ClsArgs& a, int fmt, dim3 grid, hipStream_t s) {
   else if (fmt == GP_FMT_F16) cls_attn_partial_kernel<D, true, true><<<grid, kChunk, 0, s>>>(a);
   else cls_attn_partial_kernel<D, true, false><<<grid, kChunk, 0, s>>>(a);
 }
+void launch_partial_maps(const ClsArgs& a, int fmt, dim3 grid, hipStream_t s) {
+  if (fmt == GP_FMT_BF16) cls_attn_partial_maps_kernel<false, false><<<grid, kChunk, 0, s>>>(a);
+  else if (fmt == GP_FMT_F16) cls_attn_partial_maps_kernel<true, true><<<grid, kChunk, 0, s>>>(a);
+  else cls_attn_partial_maps_kernel<true, false><<<grid, kChunk, 0, s>>>(a);
+}
+
+// the shared body of the three entry points.  map_off == NULL: one row map of [max_len] for every slide (or none),
+// map_rows rows per slide; else one map per slide and map_rows rows in the whole compact buffer.
+int cls_attn_impl(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t row_stride,
+                  const int64_t* slide_off, const int64_t* slide_len, int64_t nslide, int64_t max_len,
+                  const int32_t* row_map, const int64_t* map_off, int64_t map_rows, int H, int D,
+                  const int32_t* seg_len, const int32_t* ratios, int nbranch, float softmax_scale,
+                  int q_log2_prescaled, int fmt, const float* ln_w, const float* ln_b, float eps, uint16_t* out,
+                  void* ws, int64_t ws_bytes, void* stream) {
+  GP_REQUIRE(fmt == GP_FMT_BF16 || fmt == GP_FMT_F16 || fmt == GP_FMT_F16_VBF16, "gp_cls_attn_merge_ln: bad fmt %d", fmt);
+  GP_REQUIRE(cls_shape_ok(max_len, nslide, H, D, nbranch),
+             "gp_cls_attn_merge_ln: bad shape (max_len %lld, nslide %lld, H %d, D %d in {48, 64, 96}, H*D <= 1536, "
+             "nbranch %d)", (long long)max_len, (long long)nslide, H, D, nbranch);
+  GP_REQUIRE(q && k && v && slide_off && slide_len && seg_len && ratios && out && ws,
+             "gp_cls_attn_merge_ln: null pointer");
+  GP_REQUIRE((ln_w == nullptr) == (ln_b == nullptr), "gp_cls_attn_merge_ln: ln_w and ln_b go together");
+  GP_REQUIRE(row_stride >= (int64_t)H * D && row_stride % 8 == 0 && gp_aligned(q, 16) && gp_aligned(k, 16) &&
+                 gp_aligned(v, 16) && gp_aligned(out, 4) && gp_aligned(ws, 16),
+             "gp_cls_attn_merge_ln: q / k / v rows must be 16-byte aligned (row_stride %% 8 == 0)");
+  ClsArgs a = {};
+  const int64_t items = cls_plan(a, max_len, H, seg_len, ratios, nbranch);
+  GP_REQUIRE(items > 0, "gp_cls_attn_merge_ln: bad segment schedule");
+  const int64_t need = nslide * items * (D + kRecHead) * (int64_t)sizeof(float);
+  GP_REQUIRE(ws_bytes >= need, "gp_cls_attn_merge_ln: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
+             (long long)need);
+  a.q = q; a.k = k; a.v = v;
+  a.row_stride = row_stride;
+  a.slide_off = slide_off;
+  a.slide_len = slide_len;
+  a.max_len = max_len;
+  a.H = H; a.D = D; a.nbranch = nbranch;
+  a.qk_scale = q_log2_prescaled ? 1.0f
+                                : (softmax_scale > 0.f ? softmax_scale : 1.0f / sqrtf((float)D)) * 1.4426950408889634f;
+  a.ln_w = ln_w; a.ln_b = ln_b; a.eps = eps;
+  a.out = out;
+  a.ws = static_cast<float*>(ws);
+  a.row_map = row_map;
+  a.map_rows = (int32_t)map_rows;
+  a.map_off = map_off;
+  hipStream_t s = gp_stream(stream);
+  const dim3 grid((unsigned)items, (unsigned)nslide);
+  if (map_off != nullptr) launch_partial_maps(a, fmt, grid, s);   // (D = 48: checked by the caller)
+  else if (D == 48) launch_partial<48>(a, fmt, grid, s);
+  else if (D == 64) launch_partial<64>(a, fmt, grid, s);
+  else launch_partial<96>(a, fmt, grid, s);
+  if (int rc = gp_check_launch("gp_cls_attn_merge_ln (partial)")) return rc;
+  const size_t lds = ((size_t)nbranch * H * D + (size_t)nbranch * H + kMergeWaves) * sizeof(float);
+  if (fmt == GP_FMT_BF16) cls_merge_ln_kernel<false><<<(unsigned)nslide, 64 * kMergeWaves, lds, s>>>(a);
+  else cls_merge_ln_kernel<true><<<(unsigned)nslide, 64 * kMergeWaves, lds, s>>>(a);
+  return gp_check_launch("gp_cls_attn_merge_ln (merge)");
+}
 
 }  // namespace
 
@@ -327,43 +404,26 @@ extern "C" int gp_cls_attn_merge_ln_map(const uint16_t* q, const uint16_t* k, co
   gp_clear_error();
   GP_REQUIRE(row_map == nullptr || (map_rows >= 1 && map_rows <= max_len),
              "gp_cls_attn_merge_ln: a row map needs 1 <= map_rows (%lld) <= max_len", (long long)map_rows);
-  GP_REQUIRE(fmt == GP_FMT_BF16 || fmt == GP_FMT_F16 || fmt == GP_FMT_F16_VBF16, "gp_cls_attn_merge_ln: bad fmt %d", fmt);
-  GP_REQUIRE(cls_shape_ok(max_len, nslide, H, D, nbranch),
-             "gp_cls_attn_merge_ln: bad shape (max_len %lld, nslide %lld, H %d, D %d in {48, 64, 96}, H*D <= 1536, "
-             "nbranch %d)", (long long)max_len, (long long)nslide, H, D, nbranch);
-  GP_REQUIRE(q && k && v && slide_off && slide_len && seg_len && ratios && out && ws,
-             "gp_cls_attn_merge_ln: null pointer");
-  GP_REQUIRE((ln_w == nullptr) == (ln_b == nullptr), "gp_cls_attn_merge_ln: ln_w and ln_b go together");
-  GP_REQUIRE(row_stride >= (int64_t)H * D && row_stride % 8 == 0 && gp_aligned(q, 16) && gp_aligned(k, 16) &&
-                 gp_aligned(v, 16) && gp_aligned(out, 4) && gp_aligned(ws, 16),
-             "gp_cls_attn_merge_ln: q / k / v rows must be 16-byte aligned (row_stride %% 8 == 0)");
-  ClsArgs a = {};
-  const int64_t items = cls_plan(a, max_len, H, seg_len, ratios, nbranch);
-  GP_REQUIRE(items > 0, "gp_cls_attn_merge_ln: bad segment schedule");
-  const int64_t need = nslide * items * (D + kRecHead) * (int64_t)sizeof(float);
-  GP_REQUIRE(ws_bytes >= need, "gp_cls_attn_merge_ln: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
-             (long long)need);
-  a.q = q; a.k = k; a.v = v;
-  a.row_stride = row_stride;
-  a.slide_off = slide_off;
-  a.slide_len = slide_len;
-  a.max_len = max_len;
-  a.H = H; a.D = D; a.nbranch = nbranch;
-  a.qk_scale = q_log2_prescaled ? 1.0f
-                                : (softmax_scale > 0.f ? softmax_scale : 1.0f / sqrtf((float)D)) * 1.4426950408889634f;
-  a.ln_w = ln_w; a.ln_b = ln_b; a.eps = eps;
-  a.out = out;
-  a.ws = static_cast<float*>(ws);
-  a.row_map = row_map;
-  a.map_rows = (int32_t)map_rows;
-  hipStream_t s = gp_stream(stream);
-  const dim3 grid((unsigned)items, (unsigned)nslide);
-  if (D == 48) launch_partial<48>(a, fmt, grid, s);
-  else if (D == 64) launch_partial<64>(a, fmt, grid, s);
-  else launch_partial<96>(a, fmt, grid, s);
-  if (int rc = gp_check_launch("gp_cls_attn_merge_ln (partial)")) return rc;
-  const size_t lds = ((size_t)nbranch * H * D + (size_t)nbranch * H + kMergeWaves) * sizeof(float);
-  if (fmt == GP_FMT_BF16) cls_merge_ln_kernel<false><<<(unsigned)nslide, 64 * kMergeWaves, lds, s>>>(a);
-  else cls_merge_ln_kernel<true><<<(unsigned)nslide, 64 * kMergeWaves, lds, s>>>(a);
-  return gp_check_launch("gp_cls_attn_merge_ln (merge)");
+  return cls_attn_impl(q, k, v, row_stride, slide_off, slide_len, nslide, max_len, row_map, nullptr, map_rows, H, D,
+                       seg_len, ratios, nbranch, softmax_scale, q_log2_prescaled, fmt, ln_w, ln_b, eps, out, ws,
+                       ws_bytes, stream);
+}
+
+extern "C" int gp_cls_attn_merge_ln_maps(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t row_stride,
+                                         const int64_t* slide_off, const int64_t* slide_len, int64_t nslide,
+                                         int64_t max_len, const int32_t* row_map, const int64_t* map_off,
+                                         int64_t map_rows, int H, int D, const int32_t* seg_len,
+                                         const int32_t* ratios, int nbranch, float softmax_scale,
+                                         int q_log2_prescaled, int fmt, const float* ln_w, const float* ln_b,
+                                         float eps, uint16_t* out, void* ws, int64_t ws_bytes, void* stream) {
+  gp_clear_error();
+  GP_REQUIRE(D == 48, "gp_cls_attn_merge_ln_maps: head dim %d unsupported (48)", D);
+  GP_REQUIRE(row_map && map_off && gp_aligned(row_map, 4) && gp_aligned(map_off, 8),
+             "gp_cls_attn_merge_ln_maps: null/misaligned row_map or map_off");
+  GP_REQUIRE(map_rows >= 1 && map_rows < (int64_t)0x7fffffff,
+             "gp_cls_attn_merge_ln_maps: the compact buffer holds map_rows = %lld rows (1 .. 2^31 - 1)",
+             (long long)map_rows);
+  return cls_attn_impl(q, k, v, row_stride, slide_off, slide_len, nslide, max_len, row_map, map_off, map_rows, H, D,
+                       seg_len, ratios, nbranch, softmax_scale, q_log2_prescaled, fmt, ln_w, ln_b, eps, out, ws,
+                       ws_bytes, stream);
 }

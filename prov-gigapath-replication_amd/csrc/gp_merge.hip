@@ -393,13 +393,19 @@ GP_DEV MergeBranch merge_entry_scalar(const MergeBranch* tab, int idx) {
 
 // kList (gp_branch_merge_ln_rows): output row b*ntok + k merges token tok_list[k] of batch b instead of token
 // tok_lo + k -- the only difference, so a listed token's row holds the bits the full merge writes for it.
+// kTab && kList (gp_branch_merge_ln_rows_varlen): tok_list holds PACKED tokens.  The tokens of one block may lie
+// in any number of slides, so nothing is derived from the block's first row: in the stage pass lane t finds the
+// slide of ITS token (binary search over tok_off, per lane) and reads that slide's table entries, so the s, m
+// and nseg that decide which rows and heads cover the token are the slide's own; the slide index goes to LDS and
+// the merge pass reloads the wave's scalar entries only when the next token's slide differs.
 template <int NBR, bool kH, bool kTab = false, bool kList = false>
 __global__ __launch_bounds__(256) void branch_merge_v3_kernel(const MergeArgs a, const int tpb) {
 #pragma clang fp contract(off)
-  static_assert(!(kTab && kList), "token list: [B, L] batches only");
+  constexpr bool kTabList = kTab && kList;
   constexpr int E = 768, H = 16, D = 48;
   constexpr int LS = NBR * 16 + 1;           // LDS floats per token (16 per branch entry; +1: bank spread)
   __shared__ float lse_s[kV3Tok * LS];
+  __shared__ int slide_s[kTabList ? kV3Tok : 1];   // kTabList: the slide of the block's token t
   const int nbr = NBR < GP_MAX_BRANCHES ? NBR : a.nbranch;
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
@@ -408,7 +414,7 @@ __global__ __launch_bounds__(256) void branch_merge_v3_kernel(const MergeArgs a,
   // kTab (packed slides): the slide of the block's first token (wave-uniform binary search); a block of at most
   // kV3Tok tokens meets at most two slides (every slide holds more tokens than that, checked by the launch)
   int slide0 = 0;
-  if constexpr (kTab) {
+  if constexpr (kTab && !kList) {
     int lo = 0, hi = a.nslide - 1;
     while (lo < hi) {
       const int mid = (lo + hi + 1) >> 1;
@@ -417,7 +423,34 @@ __global__ __launch_bounds__(256) void branch_merge_v3_kernel(const MergeArgs a,
     slide0 = __builtin_amdgcn_readfirstlane(lo);
   }
   // ---- stage: lane t loads, for token row0 + t, the covered heads' lse of every branch (wave w: heads h' = w mod 4)
-  if constexpr (!kTab) {
+  if constexpr (kTabList) {
+    if (lane < tpb) {
+      const int tl = lane;
+      const int row = row0 + tl;
+      const int pk = list_token(a, row < total ? row : total - 1);   // packed token, held inside [0, T)
+      int lo = 0, hi = a.nslide - 1;
+      while (lo < hi) {                      // the token's slide: last one with tok_off <= pk
+        const int mid = (lo + hi + 1) >> 1;
+        if ((int64_t)pk >= a.tok_off[mid]) lo = mid; else hi = mid - 1;
+      }
+      if (wv == 0) slide_s[tl] = lo;
+      const int p = pk - (int)a.tok_off[lo];
+      const MergeBranch* const sb = a.mtab + (int64_t)lo * a.nbranch;
+#pragma unroll
+      for (int b = 0; b < NBR; ++b) {
+        if (b < nbr) {
+          const GpBranch g = sb[b].g;
+          const int pn = (int)div_magic((uint32_t)p, sb[b].dg);
+          const int pt = p - pn * g.g;
+          const int pi = (int)div_magic((uint32_t)pt, sb[b].dr);
+          const int pj = pt - pi * g.r;
+          const float* lrow = sb[b].lse + (size_t)(uint32_t)pn * (uint32_t)(H * g.m) + (uint32_t)pi;
+          for (int hq = wv; hq < g.hpg; hq += 4)
+            lse_s[tl * LS + b * 16 + hq] = lrow[(size_t)(uint32_t)(pj * g.hpg + hq) * (uint32_t)g.m];
+        }
+      }
+    }
+  } else if constexpr (!kTab) {
     if (lane < tpb) {
       const int tl = lane;
       const int row = row0 + tl;
@@ -505,7 +538,9 @@ __global__ __launch_bounds__(256) void branch_merge_v3_kernel(const MergeArgs a,
   // the next slide happens at most once)
   MergeBranch tb[kTab ? NBR : 1];
   int t_sl = 0, t_base = 0, t_bnd = INT_MAX;
-  if constexpr (kTab) {
+  if constexpr (kTabList) {
+    t_sl = -1;                               // (no slide yet: the first token loads its entries)
+  } else if constexpr (kTab) {
     t_sl = slide0;
     t_base = (int)a.tok_off[slide0];
     t_bnd = slide0 + 1 < a.nslide ? (int)a.tok_off[slide0 + 1] : INT_MAX;
@@ -518,7 +553,17 @@ __global__ __launch_bounds__(256) void branch_merge_v3_kernel(const MergeArgs a,
     const int row = row0 + t;
     if (t >= tpb || row >= total) break;
     int bidx = 0, p;
-    if constexpr (kTab) {
+    if constexpr (kTabList) {
+      const int sl = __builtin_amdgcn_readfirstlane(slide_s[t]);
+      if (sl != t_sl) {                      // (an ascending list changes slide at most nslide - 1 times in all)
+        t_sl = sl;
+        t_base = (int)a.tok_off[sl];
+#pragma unroll
+        for (int b = 0; b < NBR; ++b)
+          if (b < nbr) tb[b] = merge_entry_scalar(a.mtab, sl * a.nbranch + b);
+      }
+      p = list_token(a, row) - t_base;
+    } else if constexpr (kTab) {
       if (row >= t_bnd) {                    // this wave's tokens crossed into the next slide (rare): switch tables
         t_sl += 1;
         t_base = t_bnd;
@@ -759,6 +804,46 @@ extern "C" int gp_branch_merge_ln_rows(const uint16_t* const* o_in, const float*
   if (fmt == GP_FMT_F16) branch_merge_v3_kernel<5, true, false, true><<<sh.grid, 256, 0, s>>>(a, sh.tpb);
   else branch_merge_v3_kernel<5, false, false, true><<<sh.grid, 256, 0, s>>>(a, sh.tpb);
   return gp_check_launch("gp_branch_merge_ln_rows");
+}
+
+// the listed-token merge of packed slides: gp_varlen_plan's tables (slide of a token, that slide's branch entries)
+// and a list of packed tokens; branch_merge_v3_kernel alone, as gp_branch_merge_ln_rows
+extern "C" int gp_branch_merge_ln_rows_varlen(const void* plan_host, const void* plan_dev, const int32_t* rows,
+                                              int64_t n_rows, const float* ln_w, const float* ln_b, float eps,
+                                              uint16_t* out, int fmt, void* stream) {
+  GP_REQUIRE(fmt == GP_FMT_BF16 || fmt == GP_FMT_F16, "gp_branch_merge_ln_rows_varlen: bad fmt %d", fmt);
+  GP_REQUIRE(plan_host && plan_dev && gp_aligned(plan_dev, 16), "gp_branch_merge_ln_rows_varlen: null/misaligned plan");
+  const VarlenHdr h = *static_cast<const VarlenHdr*>(plan_host);
+  GP_REQUIRE(h.magic == kVarlenMagic, "gp_branch_merge_ln_rows_varlen: not a gp_varlen_plan buffer");
+  GP_REQUIRE(gp_branch_merge_ln_rows_supported(h.H, h.D, h.nbranch),
+             "gp_branch_merge_ln_rows_varlen: H %d, D %d, %d branches unsupported (16, 48, 5)", h.H, h.D, h.nbranch);
+  GP_REQUIRE(n_rows >= 0 && n_rows <= h.T, "gp_branch_merge_ln_rows_varlen: %lld rows of %lld packed tokens",
+             (long long)n_rows, (long long)h.T);
+  if (n_rows == 0) return 0;
+  GP_REQUIRE(rows && out, "gp_branch_merge_ln_rows_varlen: null pointer");
+  GP_REQUIRE(ln_w == nullptr || ln_b != nullptr, "gp_branch_merge_ln_rows_varlen: ln_w without ln_b");
+  GP_REQUIRE(gp_aligned(rows, 4) && gp_aligned(out, 16),
+             "gp_branch_merge_ln_rows_varlen: rows must be 4-byte and out 16-byte aligned");
+  // the kernel's 32-bit byte offsets run from each slide's own o region
+  const MergeBranch* mh = reinterpret_cast<const MergeBranch*>(static_cast<const char*>(plan_host) + h.mtab_off);
+  for (int x = 0; x < h.nslide * h.nbranch; ++x)
+    GP_REQUIRE((uint64_t)mh[x].g.nseg * mh[x].g.m * 1536u < (1ull << 32),
+               "gp_branch_merge_ln_rows_varlen: a slide's o rows pass 4 GiB");
+  MergeArgs a;
+  memset(&a, 0, sizeof(a));
+  a.B = 1; a.L = h.T; a.tok_lo = 0; a.ntok = n_rows;
+  a.dnt = make_div_magic((uint32_t)n_rows);
+  a.H = h.H; a.D = h.D; a.E = h.H * h.D; a.nbranch = h.nbranch;
+  a.ln_w = ln_w; a.ln_b = ln_b; a.eps = eps; a.out = out;
+  a.mtab = reinterpret_cast<const MergeBranch*>(static_cast<const char*>(plan_dev) + h.mtab_off);
+  a.tok_off = reinterpret_cast<const int64_t*>(static_cast<const char*>(plan_dev) + h.tok_off_off);
+  a.nslide = h.nslide;
+  a.tok_list = rows;
+  hipStream_t s = gp_stream(stream);
+  const MergeV3Shape sh = merge_v3_launch_shape(n_rows, attn_num_cus(s));
+  if (fmt == GP_FMT_F16) branch_merge_v3_kernel<5, true, true, true><<<sh.grid, 256, 0, s>>>(a, sh.tpb);
+  else branch_merge_v3_kernel<5, false, true, true><<<sh.grid, 256, 0, s>>>(a, sh.tpb);
+  return gp_check_launch("gp_branch_merge_ln_rows_varlen");
 }
 
 // the packed-slide (varlen) merge: the plan is gp_varlen_plan's (gp_attn.hip; layout in gp_attn_plan.h)

@@ -68,6 +68,12 @@ SIGNATURES = {
     "gp_attn_rows_plan": [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
                           c_vp, c_i64],
     "gp_dilated_attn_fwd_rows": [c_vp, c_vp, c_i32, c_i32, c_vp],
+    "gp_attn_rows_plan_varlen_bytes": [c_vp, c_i32, c_vp, c_vp, c_i32],
+    "gp_attn_rows_plan_varlen": [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                 c_vp, c_i64],
+    "gp_branch_merge_ln_rows_varlen": [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_f32, c_vp, c_i32, c_vp],
+    "gp_cls_attn_merge_ln_maps": [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32,
+                                  c_vp, c_vp, c_i32, c_f32, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp, c_i64, c_vp],
     "gp_branch_merge_ln_rows_supported": [c_i32, c_i32, c_i32],
     "gp_branch_merge_ln_rows": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp,
                                 c_f32, c_vp, c_i32, c_vp],
@@ -118,6 +124,7 @@ _RESTYPES = {"gp_last_error_string": ctypes.c_char_p, "gp_varlen_plan_bytes": c_
              "gp_linear_wgrad_workspace_bytes": c_i64,
              "gp_varlen_bwd_plan_bytes": c_i64,
              "gp_cls_attn_workspace_bytes": c_i64, "gp_attn_rows_plan_bytes": c_i64,
+             "gp_attn_rows_plan_varlen_bytes": c_i64,
              "gp_seg_attn_bwd_workspace_bytes": ctypes.c_size_t,
              "gp_dilated_attn_bwd_workspace_bytes": ctypes.c_size_t,
              "gp_gelu_layernorm_bwd_workspace_bytes": ctypes.c_size_t,
@@ -479,7 +486,8 @@ def cls_attn_workspace_bytes(max_len, nslide, H, D, segs, ratios) -> int:
 
 
 def cls_attn_merge_ln(q, k, v, row_stride, slide_off, slide_len, max_len, H, D, segs, ratios, ln_w, ln_b, eps, out,
-                      ws, softmax_scale=0.0, q_log2_prescaled=False, v_bf16=False, row_map=None, map_rows=0):
+                      ws, softmax_scale=0.0, q_log2_prescaled=False, v_bf16=False, row_map=None, map_rows=0,
+                      map_off=None):
     """out[i] = inner_attn_ln(merge(branches)) of slide i's CLS token (gp_cls_attn_merge_ln): slide_off / slide_len
     [nslide] int64 device tensors (row of token 0, length <= max_len); out [nslide, H*D] in q's format; ws: a
     uint8 tensor of cls_attn_workspace_bytes(...).  v_bf16: as dilated_attn_fwd.  row_map ([max_len] int32 device
@@ -495,6 +503,18 @@ def cls_attn_merge_ln(q, k, v, row_stride, slide_off, slide_len, max_len, H, D, 
     if slide_len.numel() != n or out.numel() != n * H * D:
         raise ValueError("cls_attn_merge_ln: slide_off, slide_len and out [nslide, H*D] disagree on nslide")
     _dev(out, q.dtype, "out"); _dev(ws, torch.uint8, "ws")
+    if map_off is not None:
+        # one map per slide (gp_cls_attn_merge_ln_maps): row_map concatenated, map_off [nslide] int64 device tensor,
+        # map_rows the rows of the whole compact buffer
+        _dev(row_map, torch.int32, "row_map"); _dev(map_off, torch.int64, "map_off")
+        if map_off.numel() != n:
+            raise ValueError("cls_attn_merge_ln: map_off must hold one offset per slide")
+        _check(lib.gp_cls_attn_merge_ln_maps(_ptr(q), _ptr(k), _ptr(v), row_stride, _ptr(slide_off), _ptr(slide_len),
+                                             n, int(max_len), _ptr(row_map), _ptr(map_off), int(map_rows), H, D,
+                                             _i32_array(segs), _i32_array(ratios), len(segs), float(softmax_scale),
+                                             int(bool(q_log2_prescaled)), fmt, _ptr(ln_w), _ptr(ln_b), eps,
+                                             _ptr(out), _ptr(ws), ws.numel(), _stream()), "gp_cls_attn_merge_ln_maps")
+        return
     if row_map is not None:
         _dev(row_map, torch.int32, "row_map")
         if row_map.numel() < int(max_len):
@@ -838,7 +858,44 @@ class AttnRowsPlan:
         self._keep = (qkv, list(outs), list(lses), offs)
 
 
-def dilated_attn_fwd_rows(plan: AttnRowsPlan, q_log2_prescaled: bool = True, v_bf16: bool = False):
+class AttnRowsPlanVarlen:
+    """AttnRowsPlan for the packed slides of a bound VarlenPlan (gp_attn_rows_plan_varlen): every slide has its own
+    lists.  groups: per branch (off, rows) int32 numpy arrays, slide-major -- off holds sum_i nseg_ib * r_b + 1
+    offsets, the groups of slide i after those of the slides before it, group (n, j) at n * r_b + j; rows the
+    concatenated ascending sparse-row lists.  Launched by dilated_attn_fwd_rows."""
+
+    def __init__(self, vplan: VarlenPlan, groups):
+        lib = load_library()
+        if vplan.host is None:
+            raise ValueError("AttnRowsPlanVarlen: the VarlenPlan must be bound (bind(qkv, outs, lses))")
+        qkv, outs, lses = vplan._keep
+        nb = len(vplan.segs)
+        if len(groups) != nb:
+            raise ValueError("AttnRowsPlanVarlen: one (off, rows) pair per branch")
+        self.fmt = vplan.fmt
+        offs = [np.ascontiguousarray(g[0], dtype=np.int32) for g in groups]
+        for b, (sl, r) in enumerate(zip(vplan.segs, vplan.ratios)):
+            ngrp = sum(-(-L // min(int(sl), L)) * int(r) for L in vplan.Ls)
+            if offs[b].size != ngrp + 1 or int(offs[b][-1]) != np.asarray(groups[b][1]).size:
+                raise ValueError("AttnRowsPlanVarlen: branch %d offsets do not match the slides' geometry / list" % b)
+        self.rows = [torch.from_numpy(np.ascontiguousarray(g[1], dtype=np.int32) if len(g[1]) else
+                                      np.zeros(1, np.int32)).to(qkv.device) for g in groups]
+        segs, ratios = _i32_array(vplan.segs), _i32_array(vplan.ratios)
+        nbytes = int(lib.gp_attn_rows_plan_varlen_bytes(vplan._L, len(vplan.Ls), segs, ratios, nb))
+        if nbytes < 0:
+            raise ValueError("AttnRowsPlanVarlen: bad shape")
+        host = (ctypes.c_uint8 * nbytes)()
+        off_ptrs = (c_vp * nb)(*[o.ctypes.data for o in offs])
+        _check(lib.gp_attn_rows_plan_varlen(vplan._L, len(vplan.Ls), vplan.H, vplan.D, segs, ratios, nb, _ptr(qkv),
+                                            qkv.stride(0), off_ptrs, _ptr_array(self.rows), _ptr_array(outs),
+                                            _ptr_array(lses), host, nbytes), "gp_attn_rows_plan_varlen")
+        self.host = host
+        self.dev = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(qkv.device)
+        self._keep = (vplan, offs)
+
+
+def dilated_attn_fwd_rows(plan, q_log2_prescaled: bool = True, v_bf16: bool = False):
+    """plan: an AttnRowsPlan or an AttnRowsPlanVarlen."""
     lib = load_library()
     fmt = FMT_F16_VBF16 if (v_bf16 and plan.fmt == FMT_F16) else plan.fmt
     _check(lib.gp_dilated_attn_fwd_rows(plan.host, _ptr(plan.dev), int(bool(q_log2_prescaled)), fmt, _stream()),
@@ -859,6 +916,19 @@ def branch_merge_ln_varlen(plan: VarlenPlan, ln_w, ln_b, eps, out):
         raise TypeError("branch_merge_ln_varlen: out must be in the plan's 16-bit format")
     _check(lib.gp_branch_merge_ln_varlen(plan.host, _ptr(plan.dev), _ptr(ln_w), _ptr(ln_b), eps, _ptr(out),
                                          plan.fmt, _stream()), "gp_branch_merge_ln_varlen")
+
+
+def branch_merge_ln_rows_varlen(plan: VarlenPlan, rows, ln_w, ln_b, eps, out):
+    """branch_merge_ln_varlen for the packed tokens rows[k] ([n] int32 device tensor, ascending): out [n, H*D]."""
+    lib = load_library()
+    _dev(out, name="out"); _dev(rows, torch.int32, "rows")
+    if fmt_of(out.dtype) != plan.fmt:
+        raise TypeError("branch_merge_ln_rows_varlen: out must be in the plan's 16-bit format")
+    if out.numel() != rows.numel() * plan.H * plan.D:
+        raise ValueError("branch_merge_ln_rows_varlen: out must be [len(rows), H*D]")
+    _check(lib.gp_branch_merge_ln_rows_varlen(plan.host, _ptr(plan.dev), _ptr(rows), rows.numel(), _ptr(ln_w),
+                                              _ptr(ln_b), eps, _ptr(out), plan.fmt, _stream()),
+           "gp_branch_merge_ln_rows_varlen")
 
 
 class VarlenBwdHdr(ctypes.Structure):

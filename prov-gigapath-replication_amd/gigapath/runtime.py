@@ -1111,9 +1111,10 @@ class ClsRows:
                                    dtype=torch.uint8, device=dev)
 
 
-def key_row_plan(L: int, segs: Sequence[int], ratios: Sequence[int]):
+def key_row_plan(L: int, segs: Sequence[int], ratios: Sequence[int], rows=None):
     """The tokens whose K / V the CLS query of a slide of L tokens reads: branch (sl, r) with
-    s = min(sl, L), m = ceil(s / r) attends tokens 0, r, ..., (m - 1) r.  Returns (rows, row_map, groups):
+    s = min(sl, L), m = ceil(s / r) attends tokens 0, r, ..., (m - 1) r.  rows: an ascending token list to plan for
+    instead of that set (a packed slide that lists all of its tokens).  Returns (rows, row_map, groups):
       rows     sorted int32 array S, the union over the branches;
       row_map  int32 [L]: row_map[S[k]] = k, -1 for a token outside S;
       groups   per branch (off, idx): the sparse rows the merge reads for the tokens of S.  Token p comes from
@@ -1121,11 +1122,13 @@ def key_row_plan(L: int, segs: Sequence[int], ratios: Sequence[int]):
                dilated_attention.py:33-53; g = s, so p is that row's own query token, wherever r divides s or the
                branch has one segment); idx[off[n r + j] : off[n r + j + 1]] lists the i of that group, ascending."""
     L = int(L)
-    mark = np.zeros(L, dtype=bool)
-    for sl, r in zip(segs, ratios):
-        s, _, m = branch_geometry(L, sl, r)
-        mark[np.arange(m, dtype=np.int64) * r] = True
-    rows = np.flatnonzero(mark).astype(np.int32)
+    if rows is None:
+        mark = np.zeros(L, dtype=bool)
+        for sl, r in zip(segs, ratios):
+            s, _, m = branch_geometry(L, sl, r)
+            mark[np.arange(m, dtype=np.int64) * r] = True
+        rows = np.flatnonzero(mark)
+    rows = np.asarray(rows).astype(np.int32)
     row_map = np.full(L, -1, dtype=np.int32)
     row_map[rows] = np.arange(rows.size, dtype=np.int32)
     groups = []
@@ -1147,16 +1150,22 @@ class KeyRows:
     every slide of the [B, L] batch; slide b's rows are compact rows [b n, (b + 1) n), its CLS first.  Everything
     here is fixed by the workspace key and lives as long as the workspace: a HIP graph bakes the pointers."""
 
+    map_off = None          # (PackedKeyRows: one row map per slide)
+
     def __init__(self, dev, B: int, L: int, E: int, F: int, plan, act: torch.dtype):
         rows, row_map, self.groups = plan
-        self._attn_plan = None
         n = int(rows.size)
         self.n, self.M = n, B * n
+        self.map_rows = n                                                # gp_cls_attn_merge_ln_map's rows per slide
         self.rows = torch.from_numpy(rows).to(dev)                       # [n] int32: the tokens S
         self.row_map = torch.from_numpy(row_map).to(dev)                 # [L] int32: token -> compact row
         gather = (np.arange(B, dtype=np.int64)[:, None] * L + rows.astype(np.int64)[None, :]).reshape(-1)
         self.gather = torch.from_numpy(gather).to(dev)                   # [B n] int64: rows of ws.x
         self.off = torch.arange(B, dtype=torch.int64, device=dev) * n    # each slide's first compact row (its CLS)
+        self._buffers(dev, E, F, act)
+
+    def _buffers(self, dev, E: int, F: int, act: torch.dtype):
+        self._attn_plan = None
         M = self.M
         self.x = torch.empty(M, E, dtype=torch.float32, device=dev)
         self.a = torch.empty(M, E, dtype=act, device=dev)
@@ -1175,6 +1184,66 @@ class KeyRows:
         if self._attn_plan is None:
             self._attn_plan = _hip.AttnRowsPlan(ws.qkv, B, L, pa.H, pa.D, pa.segs, pa.ratios, self.groups,
                                                 ws.attn.outs, ws.attn.lses)
+        return self._attn_plan
+
+
+def packed_key_row_plan(Ls: Sequence[int], segs: Sequence[int], ratios: Sequence[int],
+                        max_share: Optional[float] = None):
+    """key_row_plan for every slide of a pack (host only).  Slide i of L_i tokens lists its own
+    S_i = key_row_plan(L_i, ...)[0], or all of its tokens where |S_i| > max_share * L_i (default
+    KEYROW_MAX_SHARE; a short slide: the list launch then computes what the full one would).  Returns a dict of
+    numpy arrays:
+      n        [nslide] int64: listed rows per slide
+      off      [nslide] int64: each slide's first compact row (its CLS), the running sum of n
+      rows     [M] int32, M = sum(n): the listed tokens as PACKED indices tok_off[i] + t, ascending -- the list of
+               gp_branch_merge_ln_rows_varlen and the gather index into the packed residual stream
+      row_map  [T] int32, the slides' maps concatenated: row_map[map_off[i] + t] = compact row of token t within
+               slide i (-1: not listed); map_off [nslide] int64 = tok_off[i]
+      groups   per branch (off, idx), slide-major: gp_attn_rows_plan_varlen's grp_off / grp_rows"""
+    Ls = [int(L) for L in Ls]
+    max_share = KEYROW_MAX_SHARE if max_share is None else max_share
+    plans = []
+    for L in Ls:
+        p = key_row_plan(L, segs, ratios)
+        if p[0].size > max_share * L:
+            p = key_row_plan(L, segs, ratios, rows=np.arange(L))
+        plans.append(p)
+    n = np.array([p[0].size for p in plans], dtype=np.int64)
+    tok_off = np.concatenate([[0], np.cumsum(Ls)]).astype(np.int64)
+    groups = []
+    for b in range(len(segs)):
+        sizes = np.array([p[2][b][1].size for p in plans], dtype=np.int64)
+        base = np.concatenate([[0], np.cumsum(sizes)])
+        off = np.concatenate([p[2][b][0][:-1].astype(np.int64) + base[i] for i, p in enumerate(plans)] + [base[-1:]])
+        groups.append((off.astype(np.int32), np.concatenate([p[2][b][1] for p in plans]).astype(np.int32)))
+    return {"n": n, "off": np.concatenate([[0], np.cumsum(n)[:-1]]).astype(np.int64),
+            "rows": np.concatenate([p[0].astype(np.int64) + tok_off[i] for i, p in enumerate(plans)]).astype(np.int32),
+            "row_map": np.concatenate([p[1] for p in plans]), "map_off": tok_off[:-1].copy(), "groups": groups}
+
+
+class PackedKeyRows(KeyRows):
+    """KeyRows of a PackedWorkspace: every slide has its own row list (packed_key_row_plan), so the compact rows of
+    slide i are [off[i], off[i] + n_i), its CLS first; rows holds packed token indices; row_map / map_off are
+    gp_cls_attn_merge_ln_maps' per-slide maps and map_rows the rows of the whole compact buffer."""
+
+    def __init__(self, dev, plan, E: int, F: int, act: torch.dtype):
+        self.groups = plan["groups"]
+        self.ns = [int(v) for v in plan["n"]]
+        self.n, self.M = None, int(plan["n"].sum())
+        self.map_rows = self.M
+        self.rows = torch.from_numpy(plan["rows"]).to(dev)               # [M] int32 packed tokens
+        self.gather = self.rows.to(torch.int64)                          # ... as the gather index into ws.x
+        self.row_map = torch.from_numpy(plan["row_map"]).to(dev)         # [T] int32
+        self.map_off = torch.from_numpy(plan["map_off"]).to(dev)         # [nslide] int64
+        self.off = torch.from_numpy(plan["off"]).to(dev)                 # [nslide] int64
+        self._buffers(dev, E, F, act)
+
+    def attn_rows_plan(self, ws, pa: "PackedAttention", B: int, L: int):
+        """As KeyRows.attn_rows_plan, over ws.attn's bound VarlenPlan; None: the full varlen launch runs."""
+        if not pa.prescaled or pa.D != 48 or (ws.qkv.dtype == torch.float16 and not pa.v_bf16):
+            return None
+        if self._attn_plan is None:
+            self._attn_plan = _hip.AttnRowsPlanVarlen(ws.attn.plan, self.groups)
         return self._attn_plan
 
 
@@ -1250,8 +1319,20 @@ class PackedWorkspace(Workspace):
     def _slides(self):
         return self.tok_off[:-1], self.Ls
 
-    def key_rows(self):
-        return None          # (the packed forward keeps the full second-to-last layer)
+    def key_rows(self) -> Optional[PackedKeyRows]:
+        """The packed key-row tail's buffers, or None: KEYROW_TAIL_PACKED is off (the default: the packed forward
+        keeps the full second-to-last layer), the listed merge does not cover the shape, or the slides' lists
+        together hold more than KEYROW_MAX_SHARE of the packed rows."""
+        if not KEYROW_TAIL_PACKED:
+            return None
+        if self._key_rows is None:
+            self._key_rows = False
+            E, F, H, segs, ratios, act = self.key[2:]
+            if _hip.branch_merge_ln_rows_supported(H, E // H, len(segs)):
+                plan = packed_key_row_plan(self.Ls, segs, ratios)
+                if int(plan["n"].sum()) <= KEYROW_MAX_SHARE * sum(self.Ls):
+                    self._key_rows = PackedKeyRows(self.x.device, plan, E, F, act)
+        return self._key_rows or None
 
 
 class EncoderEngine:
@@ -1344,10 +1425,10 @@ class EncoderEngine:
     def key_row_tail(self, ws, cls_rows: Optional[ClsRows]) -> Optional[KeyRows]:
         """The KeyRows run_layers(ws, ..., cls_rows=cls_rows) runs the second-to-last layer on, or None: that
         layer's output feeds only the last layer's K / V rows of the CLS query's keys and the CLS readout, so
-        with the CLS tail on it runs for those rows alone.  Not on the packed forward, the
-        residual-epilogue path, models of fewer than 3 layers, or where Workspace.key_rows() declines.  When
-        taken, ws.x keeps the output of layer depth-3 and layer depth-2's output is KeyRows.x (slide b's CLS at
-        row KeyRows.off[b])."""
+        with the CLS tail on it runs for those rows alone.  Not on the residual-epilogue path,
+        models of fewer than 3 layers, or where Workspace.key_rows() declines; on the packed forward only with
+        KEYROW_TAIL_PACKED (off by default; PackedWorkspace.key_rows).  When taken, ws.x keeps the
+        output of layer depth-3 and layer depth-2's output is KeyRows.x (slide b's CLS at row KeyRows.off[b])."""
         if cls_rows is None or not KEYROW_TAIL or len(self.layers) < 3 or self._resid_fused_path(ws):
             return None
         return ws.key_rows()
@@ -1448,6 +1529,9 @@ KEYROW_TAIL = os.environ.get("GIGAPATH_KEYROW_TAIL", "1") != "0"
 # engaged where at most this share of a slide's rows is needed (|S| <= L / 2: L >= 7,842 on the product schedule;
 # below it tests/test_gpu_cls_tail.py's on / off bit-identity of the earlier layers holds by not engaging)
 KEYROW_MAX_SHARE = 0.5
+# the key-row tail on the packed forward (forward_packed): =1 engages it where the slides' lists hold
+# at most KEYROW_MAX_SHARE of the packed rows.  Off by default; means nothing unless KEYROW_TAIL is on.
+KEYROW_TAIL_PACKED = os.environ.get("GIGAPATH_KEYROW_TAIL_PACKED", "0") == "1"
 
 
 def key_row_layer(pl: "PackedLayer", nxt: "PackedLayer", ws, kr: KeyRows, B: int, L: int):
@@ -1455,20 +1539,28 @@ def key_row_layer(pl: "PackedLayer", nxt: "PackedLayer", ws, kr: KeyRows, B: int
     of the sparse rows their merge reads (gp_dilated_attn_fwd_rows; every key is still attended to), then the
     branch merge + inner LN of the listed tokens into the compact kr.a and EncoderLayer.forward's remaining steps (encoder.py:141-162) at M = B |S| on
     kr's buffers, as residual_pair runs them.  Leaves kr.x (the layer's output rows) and kr.a = the last layer's
-    LN1 of them; ws.x keeps the layer's input."""
+    LN1 of them; ws.x keeps the layer's input.  A PackedKeyRows (ws packed, B = 1, L = T): each slide's own rows,
+    through the per-slide plan and gp_branch_merge_ln_rows_varlen."""
     pa = pl.attn
     E, F, M = pa.E, kr.f.shape[1], kr.M
+    packed = isinstance(kr, PackedKeyRows)
     plan = kr.attn_rows_plan(ws, pa, B, L)
     if plan is not None:
         with TIMER.span("keyrow_attn"):
             _hip.dilated_attn_fwd_rows(plan, True, v_bf16=pa.v_bf16)
+    elif packed:
+        with TIMER.span("attn"):
+            _hip.dilated_attn_fwd_varlen(ws.attn.plan, pa.prescaled, v_bf16=pa.v_bf16)
     else:
         with TIMER.span("attn"):
             _hip.dilated_attn_fwd(ws.qkv, ws.qkv[:, E:], ws.qkv[:, 2 * E:], 3 * E, B, L, pa.H, pa.D, pa.segs,
                                   pa.ratios, ws.attn.outs, ws.attn.lses, 0.0, pa.prescaled, v_bf16=pa.v_bf16)
     with TIMER.span("keyrow_merge"):
-        _hip.branch_merge_ln_rows(ws.attn.outs, ws.attn.lses, pa.segs, pa.ratios, B, L, kr.rows, pa.H, pa.D,
-                                  pa.ln_w, pa.ln_b, pa.ln_eps, kr.a)
+        if packed:
+            _hip.branch_merge_ln_rows_varlen(ws.attn.plan, kr.rows, pa.ln_w, pa.ln_b, pa.ln_eps, kr.a)
+        else:
+            _hip.branch_merge_ln_rows(ws.attn.outs, ws.attn.lses, pa.segs, pa.ratios, B, L, kr.rows, pa.H, pa.D,
+                                      pa.ln_w, pa.ln_b, pa.ln_eps, kr.a)
     with TIMER.span("keyrow_tail"):
         torch.index_select(ws.x, 0, kr.gather, out=kr.x)
         linear(kr.a, pa.w_o, None, None, kr.y, kr.gemm_ws)
@@ -1491,7 +1583,8 @@ def cls_tail(pl: "PackedLayer", ws, c: ClsRows, kr: Optional[KeyRows] = None):
     with TIMER.span("cls_attn"):
         _hip.cls_attn_merge_ln(q, k, v, 3 * E, off, c.len, c.max_len, pa.H, pa.D, pa.segs, pa.ratios, pa.ln_w,
                                pa.ln_b, pa.ln_eps, c.a, c.attn_ws, 0.0, pa.prescaled, v_bf16=pa.v_bf16,
-                               row_map=None if kr is None else kr.row_map, map_rows=0 if kr is None else kr.n)
+                               row_map=None if kr is None else kr.row_map, map_rows=0 if kr is None else kr.map_rows,
+                               map_off=None if kr is None else kr.map_off)
     with TIMER.span("cls_tail"):
         torch.index_select(x, 0, off, out=c.x)
         linear(c.a, pa.w_o, None, None, c.y, c.gemm_ws)

@@ -524,7 +524,8 @@ class LongNetViT(nn.Module):
             self.encoder.engine.pack(self.encoder, dev)
             key = ("packed", str(dev), int(torch.cuda.current_stream(dev).cuda_stream), Ns, x_cat.dtype,
                    c_cat.dtype, runtime.act_dtype(), bool(all_layer_embed), bool(self.global_pool),
-                   bool(runtime.CLS_TAIL), self._top_sig, self.encoder.engine._sig)
+                   bool(runtime.CLS_TAIL), bool(runtime.KEYROW_TAIL and runtime.KEYROW_TAIL_PACKED), self._top_sig,
+                   self.encoder.engine._sig)
             ent = self._graph_lookup(key)
             if ent is None and self._graph_wanted(key):
                 ent = self._capture(key, x_cat, c_cat,
@@ -614,6 +615,9 @@ class LongNetViT(nn.Module):
         pool = torch.empty(S, E, dtype=torch.float32, device=dev)
         # only the CLS rows are read: the last layer runs for them alone and leaves them in cls.x
         cls = ws.cls_rows() if (runtime.CLS_TAIL and not self.global_pool) else None
+        # ... and, with runtime.KEYROW_TAIL_PACKED, the layer before it for each slide's own key rows: its CLS rows
+        # are compact rows kr.off of kr.x
+        kr = eng.key_row_tail(ws, cls)
 
         def readout(slot: int):
             if self.global_pool:
@@ -623,6 +627,8 @@ class LongNetViT(nn.Module):
             elif cls is not None and slot == len(layers):
                 _hip.layernorm_f32(cls.x, E, top["norm_w"], top["norm_b"], top["norm_eps"], res[slot], S, E)
                 return
+            elif kr is not None and slot == len(layers) - 1:
+                torch.index_select(kr.x, 0, kr.off, out=pool)
             else:
                 torch.index_select(ws.x, 0, ws.cls_idx, out=pool)
             _hip.layernorm_f32(pool, E, top["norm_w"], top["norm_b"], top["norm_eps"], res[slot], S, E)
