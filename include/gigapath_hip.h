@@ -259,6 +259,28 @@ int gp_dilated_attn_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v,
                         uint16_t* dq, uint16_t* dk, uint16_t* dv, int64_t d_row_stride,
                         void* workspace, size_t workspace_bytes, int fmt, void* stream);
 
+/* ---- Opt-in second implementation of gp_dilated_attn_bwd (additive to ABI 13) for the product arch's training
+ * case: D = 48, q_log2_prescaled = 1, GP_FMT_BF16 or GP_FMT_F16.  The argument list, the workspace layout and size,
+ * and every point of the contract above are gp_dilated_attn_bwd's (branch weights without gradient, zero pads, rows
+ * the forward left unwritten, the zero-pad keys of the LSE, every element of dq / dk / dv for tokens [0, L) written
+ * and nothing else, fp32 accumulation within and across branches in branch order with one rounding on store, no
+ * atomics and no inter-workgroup waits so two calls give the same bits, a non-finite dmerged yields non-finite
+ * gradients; the delta correction, the rounded dS plus its rounded remainder and the corrected delta of the dK/dV
+ * kernel are kept).  The kernels differ: 8 waves x 32 own rows per work item, v_mfma_f32_32x32x16 products with d = 48
+ * contracted in three exact steps, streamed tiles by LDS-DMA, so the bits differ from
+ * gp_dilated_attn_bwd's within the same error bound.  softmax_scale is ignored (the logit is q'.k in the log2
+ * domain).  Anything outside the scope (D = 64 / 96, an unscaled q, GP_FMT_F16_VBF16, a null or misaligned pointer, a
+ * workspace that is too small, row_stride * ratio * 128 >= 2^31) returns GP_EARG before any launch, with a message
+ * naming the argument.  gp_dilated_attn_bwd2_workspace_bytes: 0 on a bad shape or D != 48.  Host only. */
+size_t gp_dilated_attn_bwd2_workspace_bytes(int64_t B, int64_t L, int H, int D, const int32_t* seg_len,
+                                            const int32_t* ratios, int nbranch);
+int gp_dilated_attn_bwd2(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t row_stride,
+                         int64_t B, int64_t L, int H, int D, const int32_t* seg_len, const int32_t* ratios,
+                         int nbranch, const uint16_t* const* o_in, const float* const* lse_in,
+                         const uint16_t* dmerged, float softmax_scale, int q_log2_prescaled,
+                         uint16_t* dq, uint16_t* dk, uint16_t* dv, int64_t d_row_stride,
+                         void* workspace, size_t workspace_bytes, int fmt, void* stream);
+
 /* Branch merge (DilatedAttention.scattering / sparse_to_dense, dilated_attention.py:33-53,
  * 100-131) fused with inner_attn_ln (:212-213):
  *   per (token p, head h): lse_b = covered ? lse_b[..] : -1e8, lse_b == 0 -> -1e8,

@@ -62,6 +62,9 @@ SIGNATURES = {
     "gp_dilated_attn_bwd_workspace_bytes": [c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32],
     "gp_dilated_attn_bwd": [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
                             c_f32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, ctypes.c_size_t, c_i32, c_vp],
+    "gp_dilated_attn_bwd2_workspace_bytes": [c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32],
+    "gp_dilated_attn_bwd2": [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
+                             c_f32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, ctypes.c_size_t, c_i32, c_vp],
     "gp_branch_merge_ln": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_i32,
                            c_vp],
     "gp_attn_rows_plan_bytes": [c_i64, c_i64, c_vp, c_vp, c_i32],
@@ -127,6 +130,7 @@ _RESTYPES = {"gp_last_error_string": ctypes.c_char_p, "gp_varlen_plan_bytes": c_
              "gp_attn_rows_plan_varlen_bytes": c_i64,
              "gp_seg_attn_bwd_workspace_bytes": ctypes.c_size_t,
              "gp_dilated_attn_bwd_workspace_bytes": ctypes.c_size_t,
+             "gp_dilated_attn_bwd2_workspace_bytes": ctypes.c_size_t,
              "gp_gelu_layernorm_bwd_workspace_bytes": ctypes.c_size_t,
              "gp_resid_drop_ln_bwd_workspace_bytes": ctypes.c_size_t}
 
@@ -422,6 +426,20 @@ def dilated_attn_bwd(q, k, v, row_stride, B, L, H, D, segs, ratios, outs, lses, 
     """Backward of dilated_attn_fwd + the no-LN branch_merge_ln (gp_dilated_attn_bwd).  q / k / v: the forward's
     (views of a fused qkv allowed); outs / lses: its per-branch outputs; dmerged [B*L, H*D] contiguous; dq / dk /
     dv: views whose rows are d_row_stride elements apart (a fused [B*L, 3E] dqkv), all in q's 16-bit dtype."""
+    _dilated_attn_bwd("gp_dilated_attn_bwd", q, k, v, row_stride, B, L, H, D, segs, ratios, outs, lses, dmerged, dq, dk,
+                      dv, d_row_stride, softmax_scale, q_log2_prescaled)
+
+
+def dilated_attn_bwd2(q, k, v, row_stride, B, L, H, D, segs, ratios, outs, lses, dmerged, dq, dk, dv, d_row_stride,
+                      softmax_scale=0.0, q_log2_prescaled=True):
+    """dilated_attn_bwd through the opt-in second implementation (gp_dilated_attn_bwd2: D = 48, a pre-scaled q, bf16
+    or fp16; anything else is an error).  Same arguments, same contract."""
+    _dilated_attn_bwd("gp_dilated_attn_bwd2", q, k, v, row_stride, B, L, H, D, segs, ratios, outs, lses, dmerged, dq,
+                      dk, dv, d_row_stride, softmax_scale, q_log2_prescaled)
+
+
+def _dilated_attn_bwd(entry, q, k, v, row_stride, B, L, H, D, segs, ratios, outs, lses, dmerged, dq, dk, dv,
+                      d_row_stride, softmax_scale, q_log2_prescaled):
     lib = load_library()
     fmt = fmt_of(q.dtype)
     for nm, t in (("q", q), ("k", k), ("v", v), ("dq", dq), ("dk", dk), ("dv", dv)):
@@ -436,12 +454,12 @@ def dilated_attn_bwd(q, k, v, row_stride, B, L, H, D, segs, ratios, outs, lses, 
         _dev(o, q.dtype, "o")
         _dev(l, torch.float32, "lse")
     sa, ra = _i32_array(segs), _i32_array(ratios)
-    need = int(lib.gp_dilated_attn_bwd_workspace_bytes(B, L, H, D, sa, ra, len(segs)))
+    need = int(getattr(lib, entry + "_workspace_bytes")(B, L, H, D, sa, ra, len(segs)))
     ws = _bwd_workspace(q.device, max(need, 256))
-    _check(lib.gp_dilated_attn_bwd(_ptr(q), _ptr(k), _ptr(v), row_stride, B, L, H, D, sa, ra, len(segs),
-                                   _ptr_array(outs), _ptr_array(lses), _ptr(dmerged), float(softmax_scale),
-                                   int(bool(q_log2_prescaled)), _ptr(dq), _ptr(dk), _ptr(dv), d_row_stride,
-                                   ws.data_ptr(), ws.numel(), fmt, _stream()), "gp_dilated_attn_bwd")
+    _check(getattr(lib, entry)(_ptr(q), _ptr(k), _ptr(v), row_stride, B, L, H, D, sa, ra, len(segs),
+                               _ptr_array(outs), _ptr_array(lses), _ptr(dmerged), float(softmax_scale),
+                               int(bool(q_log2_prescaled)), _ptr(dq), _ptr(dk), _ptr(dv), d_row_stride,
+                               ws.data_ptr(), ws.numel(), fmt, _stream()), entry)
 
 
 def branch_merge_ln(outs, lses, segs, ratios, B, L, H, D, ln_w, ln_b, eps, out):

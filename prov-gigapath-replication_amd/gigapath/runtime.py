@@ -589,8 +589,9 @@ class _DilatedAttentionGrad(torch.autograd.Function):
     module's shared AttentionScratch would be overwritten by the next forward."""
 
     @staticmethod
-    def forward(ctx, qkv, B, L, H, D, segs, ratios, prescaled, softmax_scale):
+    def forward(ctx, qkv, B, L, H, D, segs, ratios, prescaled, softmax_scale, bwd2=False):
         E = H * D
+        ctx.bwd2 = bool(bwd2)
         qkv = qkv.contiguous()
         dev, act = qkv.device, qkv.dtype
         outs, lses = [], []
@@ -615,21 +616,24 @@ class _DilatedAttentionGrad(torch.autograd.Function):
         outs, lses = list(rest[:len(segs)]), list(rest[len(segs):])
         dout = dout.to(qkv.dtype).contiguous()
         dqkv = torch.empty_like(qkv)
-        _hip.dilated_attn_bwd(qkv, qkv[:, E:], qkv[:, 2 * E:], 3 * E, B, L, H, D, segs, ratios, outs, lses, dout,
-                              dqkv, dqkv[:, E:], dqkv[:, 2 * E:], 3 * E, softmax_scale, prescaled)
-        return (dqkv,) + (None,) * 8
+        bwd = _hip.dilated_attn_bwd2 if ctx.bwd2 else _hip.dilated_attn_bwd
+        bwd(qkv, qkv[:, E:], qkv[:, 2 * E:], 3 * E, B, L, H, D, segs, ratios, outs, lses, dout,
+            dqkv, dqkv[:, E:], dqkv[:, 2 * E:], 3 * E, softmax_scale, prescaled)
+        return (dqkv,) + (None,) * 9
 
 
 def dilated_attention_grad(qkv: torch.Tensor, B: int, L: int, H: int, D: int, segs, ratios, prescaled: bool,
-                           softmax_scale: float = 0.0) -> torch.Tensor:
+                           softmax_scale: float = 0.0, bwd2: bool = False) -> torch.Tensor:
     """qkv [B*L, 3E] 16-bit (q | k | v; with prescaled, q already times D^-0.5 log2 e) -> merged [B*L, E], the LSE
     merge of every dilation branch before inner_attn_ln, with a native backward to qkv.  The branch weights take
-    no gradient, as in the reference (dilated_attention.py:119-124)."""
+    no gradient, as in the reference (dilated_attention.py:119-124).  bwd2: take the backward from
+    gp_dilated_attn_bwd2 where the call is in its scope (D = 48, a pre-scaled q); otherwise the
+    backward is gp_dilated_attn_bwd's, silently."""
     if qkv.dtype not in _hip.ACT_DTYPES or qkv.dim() != 2 or qkv.shape != (B * L, 3 * H * D):
         raise ValueError("dilated_attention_grad: qkv must be [B*L, 3*H*D] bf16 or fp16, got %s %s"
                          % (tuple(qkv.shape), qkv.dtype))
     return _DilatedAttentionGrad.apply(qkv, B, L, H, D, list(segs), list(ratios), bool(prescaled),
-                                       float(softmax_scale))
+                                       float(softmax_scale), bool(bwd2) and D == 48 and bool(prescaled))
 
 
 class _DilatedAttentionVarlenGrad(torch.autograd.Function):
@@ -759,6 +763,18 @@ def dgrad_enabled(module: torch.nn.Module) -> bool:
     """The module's own switch (set by LongNetViT.enable_training(native_dgrad=...)), else the environment's."""
     own = getattr(module, "native_dgrad", None)
     return TRAIN_DGRAD if own is None else bool(own)
+
+
+# The dense [B, L] attention backward from gp_dilated_attn_bwd2 (DESIGN §3.18) instead of gp_dilated_attn_bwd, where
+# the call is in its scope (D = 48, a pre-scaled q; the packed path keeps its kernels).  Opt-in:
+# GIGAPATH_TRAIN_ATTN_BWD2=1, or per model LongNetViT.enable_training(native_attn_bwd2=True).
+TRAIN_ATTN_BWD2 = os.environ.get("GIGAPATH_TRAIN_ATTN_BWD2", "0") == "1"
+
+
+def attn_bwd2_enabled(module: torch.nn.Module) -> bool:
+    """The module's own switch (set by LongNetViT.enable_training(native_attn_bwd2=...)), else the environment's."""
+    own = getattr(module, "native_attn_bwd2", None)
+    return TRAIN_ATTN_BWD2 if own is None else bool(own)
 
 
 def _linear_parts_act(parts, act):

@@ -132,7 +132,7 @@ class LongNetViT(nn.Module):
 
     # ---------------------------------------------------------------- training opt-in
     def enable_training(self, flag: bool = True, native_wgrad: Optional[bool] = None,
-                        native_dgrad: Optional[bool] = None):
+                        native_dgrad: Optional[bool] = None, native_attn_bwd2: Optional[bool] = None):
         """Opt this model, its encoder, every layer and every FFN in to (or out of) the differentiable path.
         The path is taken only under autograd; inference calls are unchanged either way.
         native_wgrad: the projections' parameter gradients (patch projection, QKV, out-proj, fc1, fc2) from
@@ -140,7 +140,10 @@ class LongNetViT(nn.Module):
         model, its attentions and its FFNs; None leaves it as it is (never set: the environment's GIGAPATH_TRAIN_WGRAD,
         default off).
         native_dgrad: the same switch for the projections' input gradients (QKV, out-proj, fc1, fc2) from
-        gp_linear_dgrad instead of torch's GEMM (the environment's GIGAPATH_TRAIN_DGRAD, default off)."""
+        gp_linear_dgrad instead of torch's GEMM (the environment's GIGAPATH_TRAIN_DGRAD, default off).
+        native_attn_bwd2: the same switch on every DilatedAttention for the attention backward from
+        gp_dilated_attn_bwd2 where it applies (D = 48, a dense [B, L] batch; the environment's
+        GIGAPATH_TRAIN_ATTN_BWD2, default off)."""
         for m in self.modules():
             if hasattr(type(m), "trainable"):
                 m.trainable = bool(flag)
@@ -148,6 +151,8 @@ class LongNetViT(nn.Module):
                 m.native_wgrad = bool(native_wgrad)
             if native_dgrad is not None and hasattr(type(m), "native_dgrad"):
                 m.native_dgrad = bool(native_dgrad)
+            if native_attn_bwd2 is not None and hasattr(type(m), "native_attn_bwd2"):
+                m.native_attn_bwd2 = bool(native_attn_bwd2)
         return self
 
     def _patch_proj_grad(self, x2d, act):

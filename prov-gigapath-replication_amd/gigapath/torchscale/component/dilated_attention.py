@@ -24,6 +24,7 @@ from ... import runtime
 class DilatedAttention(nn.Module):
     native_wgrad = None     # projections' dW / db from gp_linear_wgrad: None = GIGAPATH_TRAIN_WGRAD (enable_training)
     native_dgrad = None     # projections' dX from gp_linear_dgrad: None = GIGAPATH_TRAIN_DGRAD (enable_training)
+    native_attn_bwd2 = None  # backward from gp_dilated_attn_bwd2: None = GIGAPATH_TRAIN_ATTN_BWD2 (enable_training)
 
     def __init__(self, args, embed_dim, num_heads, dropout=0.0, self_attention=False,
                  encoder_decoder_attention=False, subln=False):
@@ -101,7 +102,8 @@ class DilatedAttention(nn.Module):
                                                            self.args.dilated_ratio)
         else:
             merged = runtime.dilated_attention_grad(qkv, B, L, H, D, self.args.segment_length,
-                                                    self.args.dilated_ratio, prescaled)
+                                                    self.args.dilated_ratio, prescaled,
+                                                    bwd2=runtime.attn_bwd2_enabled(self))
         ln = self.inner_attn_ln
         if runtime.rows_fusable(E):
             a = runtime.layernorm_act_grad(merged, ln)        # one kernel each way, merged the only tensor saved

@@ -2,6 +2,7 @@
 shape, by two routes, both 16-bit formats, in one process:
 
   fused  runtime.dilated_attention_grad: gp_dilated_attn_fwd + gp_branch_merge_ln, backward gp_dilated_attn_bwd
+  fused2 the same forward, backward gp_dilated_attn_bwd2 (bwd2=True)
   seam   the reference's DilatedAttention core around flash_attn_func under autograd: per branch three gathers
          (zero pads), flash_attn_func (gp_seg_attn_fwd / gp_seg_attn_bwd), the scatter, then the LSE merge with
          no-grad weights -- tests/test_dilated_bwd_host.dilated_core with its index tensors built once and kept
@@ -124,29 +125,42 @@ def main():
             qkv.grad = None
             runtime.dilated_attention_grad(qkv, 1, L, H, D, SEGS, RATIOS, True).backward(dm)
 
+        def fused2():
+            qkv.grad = None
+            runtime.dilated_attention_grad(qkv, 1, L, H, D, SEGS, RATIOS, True, bwd2=True).backward(dm)
+
         def seam():
             ql.grad = kl.grad = vl.grad = None
             core(ql, kl, vl).backward(dm.view(1, L, E))
 
         for _ in range(args.warmup):
             fused()
+            fused2()
             seam()
         torch.cuda.synchronize()
-        tf, ts = [], []
+        tf, tf2, ts = [], [], []
         for _ in range(args.rounds):                                       # interleaved arms
             tf.append(timed(fused, args.iters))
+            tf2.append(timed(fused2, args.iters))
             ts.append(timed(seam, args.iters))
+        fused2()
+        g2 = qkv.grad.clone()
         mem_f, mem_s = peak_of(fused), peak_of(seam)
+        d2_rel = ((g2.float() - qkv.grad.float()).abs().max() / qkv.grad.float().abs().max()).item()
         assert torch.isfinite(qkv.grad.float()).all() and torch.isfinite(ql.grad.float()).all()
+        assert torch.isfinite(g2.float()).all()
         # the two routes compute the same gradients (dq of the fused route is with respect to q' = q qs)
         dk_rel = ((qkv.grad[:, E:2 * E].float() - kl.grad.view(L, E).float()).abs().max() /
                   kl.grad.float().abs().max()).item()
         ws = _hip.load_library().gp_dilated_attn_bwd_workspace_bytes(1, L, H, D, _hip._i32_array(SEGS),
                                                                      _hip._i32_array(RATIOS), len(SEGS)) / 2 ** 20
-        mf, ms = statistics.median(tf), statistics.median(ts)
+        mf, mf2, ms = statistics.median(tf), statistics.median(tf2), statistics.median(ts)
         rec = {"tool": "dilated_attn_bwd_bench", "fmt": fmt, "L": L, "H": H, "D": D, "segs": SEGS, "ratios": RATIOS,
                "fused_ms": round(mf, 3), "seam_ms": round(ms, 3), "seam_over_fused": round(ms / mf, 3),
+               "fused2_ms": round(mf2, 3), "fused2_over_fused": round(mf2 / mf, 3),
                "fused_ms_min_max": [round(min(tf), 3), round(max(tf), 3)],
+               "fused2_ms_min_max": [round(min(tf2), 3), round(max(tf2), 3)],
+               "dqkv_fused2_vs_fused_max_rel": round(d2_rel, 5),
                "seam_ms_min_max": [round(min(ts), 3), round(max(ts), 3)],
                "fused_peak_mib": round(mem_f, 1), "fused_workspace_mib": round(ws, 1),
                "seam_peak_mib": round(mem_s, 1),
