@@ -443,6 +443,39 @@ int gp_dilated_attn_bwd_varlen(const void* plan_host, const void* plan_dev, cons
                                uint16_t* dk, uint16_t* dv, int64_t d_row_stride, void* workspace,
                                size_t workspace_bytes, int fmt, void* stream);
 
+/* ---- Backward of the packed attention at D = 64 (additive to ABI 13): the trio above for the 24L1024d
+ * arch's head dim, on the kernel design of gp_dilated_attn_bwd2 (8 waves x 32 own rows per work item,
+ * v_mfma_f32_32x32x16 products with d = 64 contracted in four exact steps, streamed 64-row tiles by LDS-DMA).
+ * Replaces: gp_varlen_bwd_plan_bytes / gp_varlen_bwd_plan / gp_dilated_attn_bwd_varlen, which cover D = 48 and
+ * reject D = 64 -- one gp_dilated_attn_bwd call per slide there -- and gp_dilated_attn_bwd2, which rejects D = 64.
+ * Scope: D = 64, fmt GP_FMT_BF16, q_log2_prescaled = 1 (the q' = q D^-0.5 log2 e that gp_dilated_attn_fwd_varlen
+ * takes at D = 64; the gradient is taken with respect to it).  Anything else (D = 48 or 96 at the plan; GP_FMT_F16,
+ * GP_FMT_F16_VBF16 or an unscaled q at the launch) returns GP_EARG before any launch, with a message.
+ * gp_varlen_bwd2_plan_bytes / gp_varlen_bwd2_plan: the arguments, the sizing call (plan_host == NULL: only
+ *   *workspace_bytes is written, qkv / o_in / lse_in may be NULL), the workspace layout, the public head of the plan
+ *   buffer and the caller's copy to a 16-byte aligned device buffer are gp_varlen_bwd_plan's.  items[b] counts
+ *   256-row own blocks: sum_i nseg_ib * H * ceil(m_ib / 256).  Also rejected: qkv_row_stride * ratio * 128 >= 2^31
+ *   (a tile's 64 gathered rows are addressed by 32-bit byte offsets).  The buffer is not a gp_varlen_bwd_plan
+ *   buffer and neither launch accepts the other's.
+ * gp_dilated_attn_bwd2_varlen: gp_dilated_attn_bwd_varlen's arguments and contract (every row limit against the
+ *   slide's own L[i], no row of a neighbouring slide read; every element of dq / dk / dv for packed rows [0, T)
+ *   written and nothing else; fp32 accumulation within and across branches in branch order with one rounding on
+ *   store; no atomics and no inter-workgroup waits, so two calls give the same bits; a non-finite dmerged reaches
+ *   the gradients of its slide and leaves the other slides' bits), with q_log2_prescaled stated.  One rule of its
+ *   own: a row whose softmax spans a single key (m = 1: a one-token slide) has dS = 0 identically, so there dq = dk
+ *   = 0 exactly, whatever dmerged holds, and dv alone carries it (the packed D = 64 forward's o is not v in bits for
+ *   such a row, and p (dP - delta) would leave a rounding residue where the gradient is zero).  The bits are not
+ *   gp_dilated_attn_bwd's: the same error bound holds.  The launch call copies nothing from host to device.
+ *   Launches: a memset of the accumulators, the merge backward, two attention kernels per branch, the store --
+ *   whatever nslide is. */
+int64_t gp_varlen_bwd2_plan_bytes(int nslide, int nbranch);
+int gp_varlen_bwd2_plan(const int64_t* L, int nslide, int H, int D, const int32_t* seg_len, const int32_t* ratios,
+                        int nbranch, const uint16_t* qkv, int64_t qkv_row_stride, const uint16_t* const* o_in,
+                        const float* const* lse_in, void* plan_host, int64_t plan_bytes, int64_t* workspace_bytes);
+int gp_dilated_attn_bwd2_varlen(const void* plan_host, const void* plan_dev, const uint16_t* dmerged, uint16_t* dq,
+                                uint16_t* dk, uint16_t* dv, int64_t d_row_stride, void* workspace,
+                                size_t workspace_bytes, int q_log2_prescaled, int fmt, void* stream);
+
 /* ---- The CLS row of the last layer's attention (ABI 11).  With global_pool off the slide readout
  * (slide_encoder.py:213-221, outcome = self.norm(x)[:, 0]) reads one row per slide from each layer, so
  * the last layer's DilatedAttention.forward (dilated_attention.py:133-217) is needed for the CLS token

@@ -106,6 +106,10 @@ SIGNATURES = {
     "gp_varlen_bwd_plan_bytes": [c_i32, c_i32],
     "gp_varlen_bwd_plan": [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp],
     "gp_dilated_attn_bwd_varlen": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, ctypes.c_size_t, c_i32, c_vp],
+    "gp_varlen_bwd2_plan_bytes": [c_i32, c_i32],
+    "gp_varlen_bwd2_plan": [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp],
+    "gp_dilated_attn_bwd2_varlen": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, ctypes.c_size_t, c_i32, c_i32,
+                                    c_vp],
     "gp_gemm_workspace_bytes": [c_i64, c_i64, c_i64],
     "gp_linear": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_i32, c_vp],
     "gp_ffn_fc1_gelu": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i32, c_vp],
@@ -125,7 +129,7 @@ SIGNATURES = {
 }
 _RESTYPES = {"gp_last_error_string": ctypes.c_char_p, "gp_varlen_plan_bytes": c_i64, "gp_gemm_workspace_bytes": c_i64,
              "gp_linear_wgrad_workspace_bytes": c_i64,
-             "gp_varlen_bwd_plan_bytes": c_i64,
+             "gp_varlen_bwd_plan_bytes": c_i64, "gp_varlen_bwd2_plan_bytes": c_i64,
              "gp_cls_attn_workspace_bytes": c_i64, "gp_attn_rows_plan_bytes": c_i64,
              "gp_attn_rows_plan_varlen_bytes": c_i64,
              "gp_seg_attn_bwd_workspace_bytes": ctypes.c_size_t,
@@ -962,6 +966,7 @@ class VarlenBwdPlan:
     ``bind(qkv, outs, lses)`` writes the table for the forward's packed per-branch outputs (VarlenPlan's layouts)
     and copies it to the device; ``items`` are then the per-branch work-item counts.  The tensors are kept alive
     with the plan."""
+    ENTRY = "gp_varlen_bwd_plan"
 
     def __init__(self, Ls: Sequence[int], H: int, D: int, segs: Sequence[int], ratios: Sequence[int]):
         lib = load_library()
@@ -969,11 +974,11 @@ class VarlenBwdPlan:
         self.H, self.D, self.segs, self.ratios = H, D, list(segs), list(ratios)
         self._L = (c_i64 * len(self.Ls))(*self.Ls)
         ws = c_i64()
-        _check(lib.gp_varlen_bwd_plan(self._L, len(self.Ls), H, D, _i32_array(self.segs), _i32_array(self.ratios),
-                                      len(self.segs), None, 3 * H * D, None, None, None, 0, ctypes.byref(ws)),
-               "gp_varlen_bwd_plan")
+        _check(getattr(lib, self.ENTRY)(self._L, len(self.Ls), H, D, _i32_array(self.segs), _i32_array(self.ratios),
+                                        len(self.segs), None, 3 * H * D, None, None, None, 0, ctypes.byref(ws)),
+               self.ENTRY)
         self.workspace_bytes = int(ws.value)
-        self.nbytes = int(lib.gp_varlen_bwd_plan_bytes(len(self.Ls), len(self.segs)))
+        self.nbytes = int(getattr(lib, self.ENTRY + "_bytes")(len(self.Ls), len(self.segs)))
         self.T = sum(self.Ls)
         self.host = None
         self.dev = None
@@ -994,10 +999,10 @@ class VarlenBwdPlan:
                 raise ValueError("VarlenBwdPlan.bind: branch %d buffers too small" % b)
         host = (ctypes.c_uint64 * ((self.nbytes + 7) // 8))()          # 8-byte aligned
         ws = c_i64()
-        _check(lib.gp_varlen_bwd_plan(self._L, len(self.Ls), self.H, self.D, _i32_array(self.segs),
-                                      _i32_array(self.ratios), len(self.segs), _ptr(qkv), 3 * self.H * self.D,
-                                      _ptr_array(outs), _ptr_array(lses), host, self.nbytes, ctypes.byref(ws)),
-               "gp_varlen_bwd_plan")
+        _check(getattr(lib, self.ENTRY)(self._L, len(self.Ls), self.H, self.D, _i32_array(self.segs),
+                                        _i32_array(self.ratios), len(self.segs), _ptr(qkv), 3 * self.H * self.D,
+                                        _ptr_array(outs), _ptr_array(lses), host, self.nbytes, ctypes.byref(ws)),
+               self.ENTRY)
         self.host = host
         self.items = list(VarlenBwdHdr.from_buffer(host).items)[:len(self.segs)]
         self.dev = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(qkv.device)
@@ -1024,6 +1029,31 @@ def dilated_attn_bwd_varlen(plan: VarlenBwdPlan, dmerged, dq, dk, dv, d_row_stri
     _check(lib.gp_dilated_attn_bwd_varlen(plan.host, _ptr(plan.dev), _ptr(dmerged), _ptr(dq), _ptr(dk), _ptr(dv),
                                           d_row_stride, ws.data_ptr(), ws.numel(), plan.fmt, _stream()),
            "gp_dilated_attn_bwd_varlen")
+
+
+class VarlenBwd2Plan(VarlenBwdPlan):
+    """VarlenBwdPlan for dilated_attn_bwd2_varlen (gp_varlen_bwd2_plan: D = 64; ``items`` count 256-row blocks)."""
+    ENTRY = "gp_varlen_bwd2_plan"
+
+
+def dilated_attn_bwd2_varlen(plan: VarlenBwd2Plan, dmerged, dq, dk, dv, d_row_stride, q_log2_prescaled=True):
+    """dilated_attn_bwd_varlen at D = 64 in bf16 with a pre-scaled q (gp_dilated_attn_bwd2_varlen; anything else is an
+    error): same arguments, same contract."""
+    lib = load_library()
+    if not isinstance(plan, VarlenBwd2Plan) or plan.host is None:
+        raise RuntimeError("dilated_attn_bwd2_varlen: needs a bound VarlenBwd2Plan")
+    act = ACT_DTYPES[plan.fmt]
+    for nm, t in (("dq", dq), ("dk", dk), ("dv", dv)):
+        if not t.is_cuda or t.dtype != act:
+            raise TypeError("dilated_attn_bwd2_varlen: %s must be a device tensor of qkv's 16-bit dtype" % nm)
+    _dev(dmerged, act, "dmerged")
+    if dmerged.numel() != plan.T * plan.H * plan.D:
+        raise ValueError("dilated_attn_bwd2_varlen: dmerged holds %d elements, expected %d"
+                         % (dmerged.numel(), plan.T * plan.H * plan.D))
+    ws = _bwd_workspace(dmerged.device, max(plan.workspace_bytes, 256))
+    _check(lib.gp_dilated_attn_bwd2_varlen(plan.host, _ptr(plan.dev), _ptr(dmerged), _ptr(dq), _ptr(dk), _ptr(dv),
+                                           d_row_stride, ws.data_ptr(), ws.numel(), int(bool(q_log2_prescaled)),
+                                           plan.fmt, _stream()), "gp_dilated_attn_bwd2_varlen")
 
 
 # ------------------------------------------------------------------------------------------

@@ -551,11 +551,15 @@ class VarlenScratch:
         self.plan.bind(qkv, self.outs, self.lses)
 
 
-def varlen_covers(D: int, act: torch.dtype, grad: bool = False) -> bool:
+def varlen_covers(D: int, act: torch.dtype, grad: bool = False, bwd2: bool = False) -> bool:
     """Whether the packed (varlen) attention kernels cover head dim D in the 16-bit format act: D = 48 in bf16 and
     fp16, forward and backward; D = 64 in bf16, forward only (its LDS-DMA pair is bf16 only -- the fp16 caller's
     attention there is the exact kernel, one slide at a time -- and the varlen backward covers D = 48); D = 96 in
-    bf16, forward only, likewise (its pair takes the q that is not pre-scaled and scales the scores itself)."""
+    bf16, forward only, likewise (its pair takes the q that is not pre-scaled and scales the scores itself).
+    bwd2 (the opt-in second backward, attn_bwd2_enabled): D = 64 in bf16 trains packed too, through
+    gp_dilated_attn_bwd2_varlen."""
+    if D == 64 and act == torch.bfloat16 and grad and bwd2:
+        return True
     return D == 48 or (D in (64, 96) and act == torch.bfloat16 and not grad)
 
 
@@ -638,8 +642,9 @@ def dilated_attention_grad(qkv: torch.Tensor, B: int, L: int, H: int, D: int, se
 
 class _DilatedAttentionVarlenGrad(torch.autograd.Function):
     """_DilatedAttentionGrad for slides packed token-major in one [T, 3E] qkv: one varlen attention launch and one
-    varlen merge forward, one gp_dilated_attn_bwd_varlen call backward.  The packed per-branch o / lse
-    are allocated per call (a VarlenScratch bound to this qkv) and saved, as there."""
+    varlen merge forward, one gp_dilated_attn_bwd_varlen call backward (at D = 64 one
+    gp_dilated_attn_bwd2_varlen call).  The packed per-branch o / lse are allocated per call (a
+    VarlenScratch bound to this qkv) and saved, as there."""
 
     @staticmethod
     def forward(ctx, qkv, Ls, H, D, segs, ratios):
@@ -661,17 +666,23 @@ class _DilatedAttentionVarlenGrad(torch.autograd.Function):
         outs, lses = list(rest[:len(segs)]), list(rest[len(segs):])
         dout = dout.to(qkv.dtype).contiguous()
         dqkv = torch.empty_like(qkv)
-        plan = _hip.VarlenBwdPlan(Ls, H, D, segs, ratios).bind(qkv, outs, lses)
-        _hip.dilated_attn_bwd_varlen(plan, dout, dqkv, dqkv[:, E:], dqkv[:, 2 * E:], 3 * E)
+        if D == 64:                     # dilated_attention_grad_varlen admitted it: bf16 with the second backward on
+            plan = _hip.VarlenBwd2Plan(Ls, H, D, segs, ratios).bind(qkv, outs, lses)
+            _hip.dilated_attn_bwd2_varlen(plan, dout, dqkv, dqkv[:, E:], dqkv[:, 2 * E:], 3 * E)
+        else:
+            plan = _hip.VarlenBwdPlan(Ls, H, D, segs, ratios).bind(qkv, outs, lses)
+            _hip.dilated_attn_bwd_varlen(plan, dout, dqkv, dqkv[:, E:], dqkv[:, 2 * E:], 3 * E)
         return (dqkv,) + (None,) * 5
 
 
-def dilated_attention_grad_varlen(qkv: torch.Tensor, Ls: Sequence[int], H: int, D: int, segs, ratios) -> torch.Tensor:
+def dilated_attention_grad_varlen(qkv: torch.Tensor, Ls: Sequence[int], H: int, D: int, segs, ratios,
+                                  bwd2: bool = False) -> torch.Tensor:
     """qkv [T, 3E] 16-bit, the slides of lengths Ls packed token-major (q | k | v, q already times D^-0.5 log2 e)
     -> merged [T, E]: every slide's own dilated_attention_grad (its own segment schedule, no attention across
-    slides), with a native backward to qkv.  D = 48, the head dim the varlen backward covers."""
+    slides), with a native backward to qkv.  D = 48, the head dim the varlen backward covers whatever bwd2 says;
+    with bwd2 also D = 64 in bf16: the packed D = 64 forward and merge, and gp_dilated_attn_bwd2_varlen backward."""
     Ls = [int(x) for x in Ls]
-    if D != 48:
+    if D != 48 and not (D == 64 and bwd2 and qkv.dtype == torch.bfloat16):
         raise ValueError("dilated_attention_grad_varlen: the varlen kernels cover D = 48 (got %d)" % D)
     if not Ls or min(Ls) < 1:
         raise ValueError("dilated_attention_grad_varlen: every slide needs at least one token, got %s" % (Ls,))
@@ -766,7 +777,8 @@ def dgrad_enabled(module: torch.nn.Module) -> bool:
 
 
 # The dense [B, L] attention backward from gp_dilated_attn_bwd2 instead of gp_dilated_attn_bwd, where
-# the call is in its scope (D = 48, a pre-scaled q; the packed path keeps its kernels).  Opt-in:
+# the call is in its scope (D = 48, a pre-scaled q; the packed path keeps its kernels at D = 48, and at D = 64 in bf16
+# the switch is what lets a mixed-length batch train packed, through gp_dilated_attn_bwd2_varlen).  Opt-in:
 # GIGAPATH_TRAIN_ATTN_BWD2=1, or per model LongNetViT.enable_training(native_attn_bwd2=True).
 TRAIN_ATTN_BWD2 = os.environ.get("GIGAPATH_TRAIN_ATTN_BWD2", "0") == "1"
 

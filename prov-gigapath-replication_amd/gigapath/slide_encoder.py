@@ -143,7 +143,8 @@ class LongNetViT(nn.Module):
         gp_linear_dgrad instead of torch's GEMM (the environment's GIGAPATH_TRAIN_DGRAD, default off).
         native_attn_bwd2: the same switch on every DilatedAttention for the attention backward from
         gp_dilated_attn_bwd2 where it applies (D = 48, a dense [B, L] batch; the environment's
-        GIGAPATH_TRAIN_ATTN_BWD2, default off)."""
+        GIGAPATH_TRAIN_ATTN_BWD2, default off).  At D = 64 in bf16 it also makes forward_packed train the pack in one
+        pass, its backward gp_dilated_attn_bwd2_varlen, instead of slide by slide."""
         for m in self.modules():
             if hasattr(type(m), "trainable"):
                 m.trainable = bool(flag)
@@ -512,10 +513,13 @@ class LongNetViT(nn.Module):
                                "disable_sequence_parallel() first")
         if self._sp is not None and self._sp.world > 1:
             raise ValueError("forward_packed is single-device: disable sequence parallelism first")
-        if not runtime.varlen_covers(self.encoder.layers[0].self_attn.head_dim, runtime.act_dtype(), grad_path) or \
+        attn0 = self.encoder.layers[0].self_attn
+        if not runtime.varlen_covers(attn0.head_dim, runtime.act_dtype(), grad_path,
+                                     bwd2=runtime.attn_bwd2_enabled(attn0)) or \
                 len({c.dtype for c in cs}) != 1 or len({x.dtype for x in xs}) != 1:
             # the varlen kernels cover D = 48 (the 12L768d arch) and, for the bf16 inference forward, D = 64
-            # (24L1024d) and D = 96 (12L1536d); training and the fp16 caller at D = 64 / 96 run slide by slide
+            # (24L1024d) and D = 96 (12L1536d); training and the fp16 caller at D = 64 / 96 run slide by slide --
+            # but for bf16 training at D = 64 with the second attention backward switched on
             return [self.forward(x[None], c[None], all_layer_embed) for x, c in zip(xs, cs)]
         Ns = tuple(int(x.shape[0]) for x in xs)
         x_cat = torch.cat(xs, 0)

@@ -68,7 +68,8 @@ class DilatedAttention(nn.Module):
         """The differentiable path: torch projections / LayerNorm around the native core.  The Q scale
         D^-0.5 log2 e is folded into the Q weight and bias in fp32 before their cast, as PackedAttention does.
         slide_lens: the input is [1, T, E], slides of those lengths packed token-major; the core is then
-        runtime.dilated_attention_grad_varlen (every slide its own segment schedule, D = 48)."""
+        runtime.dilated_attention_grad_varlen (every slide its own segment schedule; D = 48, or D = 64 in bf16 with
+        native_attn_bwd2)."""
         B, L, E = query.shape
         H, D = self.num_heads, self.head_dim
         if slide_lens is not None and (B != 1 or L != sum(slide_lens)):
@@ -99,7 +100,8 @@ class DilatedAttention(nn.Module):
                                  for t, w, b in ((query, wq, bq), (key, wk, bk), (value, wv, bv))], 1)
         if slide_lens is not None:
             merged = runtime.dilated_attention_grad_varlen(qkv, slide_lens, H, D, self.args.segment_length,
-                                                           self.args.dilated_ratio)
+                                                           self.args.dilated_ratio,
+                                                           bwd2=runtime.attn_bwd2_enabled(self))
         else:
             merged = runtime.dilated_attention_grad(qkv, B, L, H, D, self.args.segment_length,
                                                     self.args.dilated_ratio, prescaled,

@@ -16,6 +16,12 @@ reported next to it).
 
     python tools/dilated_attn_bwd_bench.py [--L 70001] [--rounds 7] [--iters 3] [--warmup 2]
                                            [--out profiles/dilated_attn_bwd_bench.json]
+
+--varlen-d64 runs another pair of arms instead (varlen_d64 below): a mixed-length pack at D = 64 in bf16, packed
+through gp_dilated_attn_bwd2_varlen against slide by slide through gp_dilated_attn_bwd.
+
+    python tools/dilated_attn_bwd_bench.py --varlen-d64 [--pack 12001,301,...]
+                                           [--out profiles/attn_bwd2_d64_varlen_bench.json]
 """
 import argparse
 import json
@@ -100,6 +106,54 @@ def peak_of(fn):
     return (torch.cuda.max_memory_allocated() - base) / 2 ** 20
 
 
+def varlen_d64(args):
+    """--varlen-d64: forward + merge + backward of a mixed-length pack at H = 16, D = 64 in bf16 (the 24L1024d arch's
+    attention core), two arms interleaved: `packed` runtime.dilated_attention_grad_varlen(bwd2=True) -- the packed
+    D = 64 forward and merge, backward gp_dilated_attn_bwd2_varlen -- against `per_slide`, the route
+    without it: runtime.dilated_attention_grad slide by slide, backward gp_dilated_attn_bwd."""
+    dev, Dh = torch.device("cuda"), 64
+    E = H * Dh
+    Ls = [int(x) for x in args.pack.split(",")]
+    off = [0]
+    for n in Ls:
+        off.append(off[-1] + n)
+    g = torch.Generator(device=dev).manual_seed(off[-1])
+    x = torch.randn(off[-1], 3 * E, device=dev, generator=g)
+    x[:, :E] *= (Dh ** -0.5) * runtime.LOG2E
+    qkv = x.bfloat16().requires_grad_(True)
+    dm = torch.randn(off[-1], E, device=dev, generator=g).bfloat16()
+    parts = [qkv.detach()[off[i]:off[i + 1]].clone().requires_grad_(True) for i in range(len(Ls))]
+
+    def packed():
+        qkv.grad = None
+        runtime.dilated_attention_grad_varlen(qkv, Ls, H, Dh, SEGS, RATIOS, bwd2=True).backward(dm)
+
+    def per_slide():
+        for i, p in enumerate(parts):
+            p.grad = None
+            runtime.dilated_attention_grad(p, 1, Ls[i], H, Dh, SEGS, RATIOS, True).backward(dm[off[i]:off[i + 1]])
+
+    for _ in range(args.warmup):
+        packed()
+        per_slide()
+    torch.cuda.synchronize()
+    tp, ts = [], []
+    for _ in range(args.rounds):                                           # interleaved arms
+        tp.append(timed(packed, args.iters))
+        ts.append(timed(per_slide, args.iters))
+    want = torch.cat([p.grad for p in parts], 0).float()
+    assert torch.isfinite(qkv.grad.float()).all() and torch.isfinite(want).all()
+    rel = ((qkv.grad.float() - want).abs().max() / want.abs().max()).item()
+    mp, ms = statistics.median(tp), statistics.median(ts)
+    rec = {"tool": "dilated_attn_bwd_bench", "arm": "varlen_d64", "fmt": "bf16", "Ls": Ls, "T": off[-1], "H": H, "D": Dh,
+           "segs": SEGS, "ratios": RATIOS, "packed_ms": round(mp, 3), "per_slide_ms": round(ms, 3),
+           "per_slide_over_packed": round(ms / mp, 3), "packed_ms_min_max": [round(min(tp), 3), round(max(tp), 3)],
+           "per_slide_ms_min_max": [round(min(ts), 3), round(max(ts), 3)], "dqkv_packed_vs_per_slide_max_rel": round(rel, 5),
+           "rounds": args.rounds, "iters": args.iters, "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}
+    print(json.dumps(rec), flush=True)
+    return [rec]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--L", type=int, default=70001)
@@ -107,8 +161,19 @@ def main():
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--varlen-d64", action="store_true", help="the packed D = 64 arm (see varlen_d64) instead")
+    ap.add_argument("--pack", default="12001,301,4001,2,25001,801,1501,9001",
+                    help="--varlen-d64: the slides' lengths (CLS + tiles)")
     args = ap.parse_args()
     _hip.load_library()
+    if args.varlen_d64:
+        lines = varlen_d64(args)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                for rec in lines:
+                    f.write(json.dumps(rec) + "\n")
+        return
     dev = torch.device("cuda")
     L, E = args.L, H * D
     core = SeamCore(L, dev)
